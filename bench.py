@@ -26,6 +26,14 @@ generator_files.rs:24-42) on device LOCAL_RANK (mod the device count: on a
 torch.distributed (gloo).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--pool P] [--workload jpeg|cfg4|wds|png]
+
+A plain run does what the headline figure needs: it sets up, warms up, times
+`--steps` steps and prints the result line.  `--full` adds everything else
+(5 timed windows and their spread, the isolated per-kernel pass and the
+roofline figures, the host-memory and dg_decode_one legs, the CPU baselines).
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs).
+The pool images are kept in a per-user cache (synth.corpus_cache_dir);
+`--prepare` fills it ahead of the first run.
 """
 from __future__ import annotations
 
@@ -56,10 +64,20 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--hw-queues", type=int, default=0,
                     help="GPU_MAX_HW_QUEUES for this process and its ranks (0: leave the runtime's default; <= 32)")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=5,
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (per window)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: 5 timed windows, the isolated per-kernel "
+                         "pass and the roofline figures, the host-memory and dg_decode_one legs, the CPU baselines "
+                         "(a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--windows", type=int, default=0,
                     help="timed windows of --steps steps each (SURVEY §8(d): the line reports the median window, "
-                         "the others beside it as the spread)")
+                         "the others beside it as the spread); 0: 1, or 5 with --full")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(see dump_outputs)")
+    ap.add_argument("--prepare", action="store_true",
+                    help="generate the workload's whole image pool into the corpus cache and exit (no GPU needed); "
+                         "later runs on this machine load it from there")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="images per step (0: 256, or 1024 for wds's ImageNet-size JPEGs)")
     ap.add_argument("--pool", type=int, default=0,
@@ -73,11 +91,11 @@ def parse():
     ap.add_argument("--sub-bits", type=int, default=0)
     ap.add_argument("--workers", type=int, default=0, help="corpus generation processes")
     ap.add_argument("--lead-bits", type=int, default=-1, help="entropy lead-in bits (-1 = library default)")
-    ap.add_argument("--serial-steps", type=int, default=5,
+    ap.add_argument("--serial-steps", type=int, default=-1,
                     help="untimed batches run one at a time after the timed region: per-kernel times without "
-                         "the overlap of consecutive batches (roofline_isolated); 5, the batches the "
+                         "the overlap of consecutive batches (roofline_isolated); -1: 0, or with --full 5, the batches the "
                          "isolated-pass kernel trace (tools/gpu_calib.sh ISO, SERIAL=5) measures: the entropy "
-                         "stages differ by up to 30% between batches of different images")
+                         "stages differ by up to 30%% between batches of different images")
     ap.add_argument("--pmc-json", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r06",
                                                        "pmc", "pmc_traffic.json"),
                     help="per-stage HBM bytes from a PMC run of this configuration (tools/pmc_traffic.py)")
@@ -95,10 +113,12 @@ def parse():
                     help="JPEG pixel semantics: 1 zune-jpeg 0.5.12 restated (default: the reference's decoder, the "
                          "mode INTEGRATION.md sets for the drop-in), 0 libjpeg-turbo (pinned to PIL)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="wall seconds of the CPU-baseline sample (x cores of CPU work)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--e2e-steps", type=int, default=3, help="host-memory (PCIe-inclusive) steps")
-    ap.add_argument("--one-threads", type=int, default=32,
-                    help="integration path: host threads calling dg_decode_one (coalesced into GPU batches); 0 = off")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--e2e-steps", type=int, default=-1,
+                    help="host-memory (PCIe-inclusive) steps (-1: 0, or 3 with --full)")
+    ap.add_argument("--one-threads", type=int, default=-1,
+                    help="integration path: host threads calling dg_decode_one (coalesced into GPU batches); 0 = off "
+                         "(-1: 0, or 32 with --full)")
     ap.add_argument("--one-images", type=int, default=0, help="images through dg_decode_one (0: 8 batches)")
     ap.add_argument("--ctx-opt", action="append", default=[],
                     help="extra context option key=value (experiments; repeatable)")
@@ -128,6 +148,15 @@ def parse():
                          "not fit are split)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    # what only --full runs by default; a leg asked for by its own option runs either way
+    if a.windows <= 0:
+        a.windows = 5 if a.full else 1
+    if a.serial_steps < 0:
+        a.serial_steps = 5 if a.full else 0
+    if a.e2e_steps < 0:
+        a.e2e_steps = 3 if a.full else 0
+    if a.one_threads < 0:
+        a.one_threads = 32 if a.full else 0
     if a.pool <= 0:
         a.pool = {"jpeg": 4096, "cfg4": 16384, "png": 256, "wds": 0}[a.workload]
     if a.samples <= 0:
@@ -550,8 +579,68 @@ def pin_rank_cores(local: int, local_world: int):
     return mine
 
 
+def prepare(a) -> int:
+    """`--prepare`: every image of the workload's pool into the corpus cache
+    (host work only), so that the runs after it load the pool and generate
+    nothing.  The png and wds corpora are small and made in memory by each run."""
+    from datago_amd import synth
+    if a.workload not in ("jpeg", "cfg4"):
+        return 0
+    seed = 4 if a.workload == "cfg4" else 2
+    made = synth.generate_pool_images(seed, a.pool, range(a.pool), a.workers or cpu_share(), a.short_min, a.short_max,
+                                      a.progressive_frac,
+                                      progress=lambda m: print(f"[prepare] {m}", file=sys.stderr, flush=True),
+                                      restart_marker_rows=a.rst_rows)
+    print(f"bench.py: pool of {a.pool} images in {synth.corpus_cache_dir()} ({made} generated now)", file=sys.stderr)
+    return 0
+
+
+DUMP_SAMPLE = 8 << 20  # --dump-outputs: output bytes sampled over the whole batch (32 MB as float32)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(ctx, dirpath: str, last: dict, suffix: str = "") -> None:
+    """`--dump-outputs DIR`: what the caller of the timed path received from
+    its last timed step, as float .npy files (two builds run with the same
+    arguments see the same inputs, so the files compare output for output):
+
+      meta.npy          float64 (B, 8) per image: original_width, original_height,
+                        width, height, channels, status, bucket, nbytes
+      image_sums.npy    float64 (B,)   sum of each image's output bytes
+      pixels_sample.npy float32 (S,)   the batch's output bytes, image after image,
+                        at S = min(total, 8 Mi) seeded positions in ascending
+                        order (all of them when total <= 8 Mi)
+      image0.npy        float32 (H, W, C) the first image whole (raw outputs only)
+    """
+    os.makedirs(dirpath, exist_ok=True)
+    idx, outs, metas = last["idx"], np.asarray(last["outs"], np.uint64), last["metas"]
+    meta = np.asarray([[m.original_width, m.original_height, m.width, m.height, m.channels, m.status, m.bucket,
+                        m.nbytes if m.status == 0 else 0] for m in metas[:len(idx)]], np.float64)
+    host = []
+    for j in range(len(idx)):
+        buf = np.empty(int(meta[j, 7]), np.uint8)
+        if buf.size:
+            ctx.d2h(buf, int(outs[j]))
+        host.append(buf)
+    flat = np.concatenate(host) if host else np.zeros(0, np.uint8)
+    if flat.size > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.size, size=DUMP_SAMPLE))
+        sample = flat[pos]
+    else:
+        sample = flat
+    files = {"meta": meta, "image_sums": np.asarray([float(b.sum(dtype=np.uint64)) for b in host], np.float64),
+             "pixels_sample": sample.astype(np.float32)}
+    w, h, c = int(meta[0, 2]), int(meta[0, 3]), int(meta[0, 4])
+    if host and 0 < host[0].size == w * h * c <= (4 << 20):
+        files["image0"] = host[0].reshape(h, w, c).astype(np.float32)
+    for name, arr in files.items():
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), arr)
+
+
 def main() -> int:
     a = parse()
+    if a.prepare:
+        return prepare(a)
     if a.hw_queues > 0:  # before anything initialises HIP (ranks inherit it)
         os.environ["GPU_MAX_HW_QUEUES"] = str(min(a.hw_queues, 32))
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -665,7 +754,8 @@ def main() -> int:
     else:
         out_bytes = [tw * th * nc for (tw, th), (_, _, nc) in zip(targets, dims)]
     band_dec = "band_dec=1" in a.ctx_opt  # k_band_dec is off by default (library option band_dec)
-    img_stage_bytes = [png_stage_bytes(d, dim, tgt) if png else stage_bytes(L, d, dim, tgt, band_dec)
+    # per-stage algorithmic bytes feed the roofline figures only (--full)
+    img_stage_bytes = [(png_stage_bytes(d, dim, tgt) if png else stage_bytes(L, d, dim, tgt, band_dec)) if a.full else {}
                        for d, dim, tgt in zip(pool, dims, targets)]
     B_ = min(a.batch, 1 << 16)
     # output arena for one step (reused), sized for the largest B_ outputs
@@ -707,6 +797,8 @@ def main() -> int:
         ring["base"] = ctx.alloc(a.prog_ring * ring_sz)
         ring["owner"] = [-1] * a.prog_ring
 
+    last = {}
+
     def submit(k: int):
         idx = batch_idx(k)
         slot = k % a.inflight  # one output arena per batch in flight
@@ -729,6 +821,7 @@ def main() -> int:
             outs = np.asarray(outs, np.uint64)
         ticket, metas = ctx.submit_device(np.uint64(h_base) + offs_np[idx], np.uint64(d_arena) + offs_np[idx],
                                           lens_np[idx], outs, out_np[idx], forced_np[idx])
+        last.update(idx=idx, outs=outs, metas=metas)  # --dump-outputs reads the last timed step's
         return ticket, metas, idx, k
 
     def check(metas, idx, which=None):
@@ -834,6 +927,8 @@ def main() -> int:
         win.append((dt_w, acc["px"] - acc0["px"], acc["alg"] - acc0["alg"], acc["outpx"] - acc0["outpx"]))
     steps_all = a.steps * nwin
     ctx.set_option("timing", 0)
+    if a.dump_outputs:  # before the untimed legs reuse the output arenas
+        dump_outputs(ctx, a.dump_outputs, last, f"_rank{rank}" if world > 1 else "")
     # host planning phases of the timed steps only (read before the untimed legs add to them)
     host_phases = {q: round(ctx.stat("host_us_" + q) / 1e3 / steps_all, 3)
                    for q in HOST_PHASES}
@@ -1056,25 +1151,26 @@ def main() -> int:
             pass
         # measured device-to-device copy bandwidth (report the
         # roofline against it too): best of 3 copies of a 1 GiB buffer, bytes
-        # read + written over the event time
+        # read + written over the event time (--full)
         copy_gbs = None
-        try:
-            nbytes = 1 << 30
-            xs = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-            ys = torch.empty_like(xs)
-            best = None
-            for _ in range(4):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                ys.copy_(xs)
-                e1.record()
-                e1.synchronize()
-                t_ = e0.elapsed_time(e1) / 1e3
-                best = t_ if best is None else min(best, t_)
-            copy_gbs = round(2 * nbytes / best / 1e9, 1)
-            del xs, ys
-        except RuntimeError:
-            pass
+        if a.full:
+            try:
+                nbytes = 1 << 30
+                xs = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+                ys = torch.empty_like(xs)
+                best = None
+                for _ in range(4):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    ys.copy_(xs)
+                    e1.record()
+                    e1.synchronize()
+                    t_ = e0.elapsed_time(e1) / 1e3
+                    best = t_ if best is None else min(best, t_)
+                copy_gbs = round(2 * nbytes / best / 1e9, 1)
+                del xs, ys
+            except RuntimeError:
+                pass
         result = {
             "metric": ("Mpixel/s device-resident PNG decode+bucket-resize (image + aligned mask pairs)" if png else
                        "Mpixel/s device-resident JPEG decode+bucket-resize at 1/2/4/8 MI355X"),
@@ -1207,12 +1303,16 @@ def main() -> int:
             "wg_timing_us": ({f"{k}_{q}": ctx.stat(f"wg_{k}_{q}") / 1000 for k in ("sync", "write")
                               for q in ("span", "mean", "p90", "max")} if a.wg_timing else None),
         }
-        if world == 1 and not a.no_cpu_baseline:
+        result["full"] = bool(a.full)
+        if a.full and world == 1 and not a.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(pool, targets, a.cpu_seconds, a.encode, a.decode_semantics)
             result["cpu_baseline_pillow"] = pillow_baseline(pool, targets, a.cpu_seconds, a.encode)
         else:
             result["cpu_baseline"] = None
-        if png or wds:  # the PMC file is for the configs[1] workload
+        if not a.full:  # no stage byte counts, measured copy bandwidth or (by default) isolated pass to put a roofline on
+            for k_ in ("roofline", "roofline_overlapped_span", "roofline_valu"):
+                result[k_] = None
+        elif png or wds:  # the PMC file is for the configs[1] workload
             result["roofline"]["traffic"] = None
             result["roofline"]["traffic_source"] = None
         line = json.dumps(result)

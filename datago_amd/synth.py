@@ -151,11 +151,13 @@ def mixed_corpus(seed: int, n: int, short_min: int = 256, short_max: int = 2048,
 
 def corpus_cache_dir() -> str:
     """Where generated pool images are kept between runs on one machine
-    ($DATAGO_CORPUS_CACHE, default <tmp>/datago_amd_corpus): the bench's
-    back-to-back 1/2/4/8-GPU runs, and the ranks of one run, share it."""
+    ($DATAGO_CORPUS_CACHE, default the user's cache directory,
+    ${XDG_CACHE_HOME:-~/.cache}/datago_amd/corpus): the bench's back-to-back
+    1/2/4/8-GPU runs, and the ranks of one run, share it, and `bench.py
+    --prepare` fills it ahead of them."""
     import os
-    import tempfile
-    return os.environ.get("DATAGO_CORPUS_CACHE") or os.path.join(tempfile.gettempdir(), "datago_amd_corpus")
+    return os.environ.get("DATAGO_CORPUS_CACHE") or os.path.join(
+        os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"), "datago_amd", "corpus")
 
 
 def is_progressive_jpeg(data: bytes) -> bool:

@@ -23,7 +23,7 @@ if [ "${CALIB:-1}" = 1 ]; then
 fi
 if [ "${ISO:-1}" = 1 ]; then
   echo "=== isolated-pass kernel trace"
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/iso -o run -- python3 bench.py --steps 5 --windows 1 \
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/iso -o run -- python3 bench.py --full --steps 5 --windows 1 \
     --warmup 3 --serial-steps ${SERIAL:-5} --e2e-steps 0 --one-threads 0 --no-cpu-baseline ${BENCH_ARGS:-} \
     --out $OUT/iso_bench.json > $OUT/iso.log 2>&1
   rc=$?; echo "exit $rc"; [ $rc -eq 0 ] || { tail -20 $OUT/iso.log; exit $rc; }

@@ -21,7 +21,7 @@ tests)
   ;;
 bench)
   mkdir -p $OUT/bench
-  timeout -k 10 600 python bench.py --out $OUT/bench/bench.json > $OUT/bench/bench.log 2>&1
+  timeout -k 10 600 python bench.py --full --out $OUT/bench/bench.json > $OUT/bench/bench.log 2>&1
   rc=$?; echo "=== bench exit $rc"; [ $rc -eq 0 ] || { tail -20 $OUT/bench/bench.log; exit $rc; }
   python -c "import json;d=json.load(open('$OUT/bench/bench.json'));print(d['value'],d['ms_per_step'],d['roofline']['frac'],d['roofline'].get('traffic'),d['cpu_baseline']['value'],(d.get('e2e_decode_one') or {}).get('mpix_s'),d.get('e2e_host_mpix_s'))"
   OUT=$OUT/iso CALIB=0 ISO=1 SERIAL=5 tools/gpu_calib.sh || exit $?

@@ -24,7 +24,7 @@ IFS=';' read -ra LS <<< "$LIBS"
 for r in $(seq 1 $REPS); do
   for k in "${!LS[@]}"; do
     lib=${LS[$k]}; tag=lib${k}_$r
-    DG_LIB_PATH=$lib timeout -k 10 400 python bench.py --steps $STEPS --warmup 3 --e2e-steps 0 --one-threads 0 \
+    DG_LIB_PATH=$lib timeout -k 10 400 python bench.py --full --steps $STEPS --warmup 3 --e2e-steps 0 --one-threads 0 \
       --no-cpu-baseline $EXTRA --out $OUT/$tag.json > $OUT/$tag.log 2>&1
     rc=$?; echo "=== $tag [${lib:-in-tree}] exit $rc"; [ $rc -eq 0 ] || { tail -20 $OUT/$tag.log; exit $rc; }
     python -c "import json;d=json.load(open('$OUT/$tag.json'));s=d['roofline_isolated']['stages_ms'];print(d['value'],d['ms_per_step'],{k:round(v,3) for k,v in s.items() if v>0.05})"

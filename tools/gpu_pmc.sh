@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/pmc}
 mkdir -p $OUT
-ARGS="--steps ${STEPS:-2} --warmup 1 --batch ${BATCH:-256} --pool ${POOL:-4096} --inflight ${INFLIGHT:-1} ${PMC_EXTRA:-} --no-cpu-baseline --e2e-steps 0 --one-threads 0 --serial-steps 0"
+ARGS="--full --steps ${STEPS:-2} --warmup 1 --batch ${BATCH:-256} --pool ${POOL:-4096} --inflight ${INFLIGHT:-1} ${PMC_EXTRA:-} --no-cpu-baseline --e2e-steps 0 --one-threads 0 --serial-steps 0"
 run() {  # name counters...
   local name=$1; shift
   echo "=== pmc $name: $*"

@@ -12,7 +12,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   timeout -k 10 600 python -u -m pytest -x -v --timeout 120 --timeout-method thread -m gpu tests/test_gpu_png.py > $OUT/tests.log 2>&1
   rc=$?; tail -2 $OUT/tests.log; [ $rc -eq 0 ] || { grep -E "FAIL|Error" $OUT/tests.log | head -20; exit $rc; }
 fi
-A="--workload png --steps 10 --warmup 2 --windows ${WINDOWS:-3} --e2e-steps 0 --one-threads 0 --no-cpu-baseline"
+A="--full --workload png --steps 10 --warmup 2 --windows ${WINDOWS:-3} --e2e-steps 0 --one-threads 0 --no-cpu-baseline"
 for v in ${VARIANTS:-2 8 9}; do
   timeout -k 10 400 python bench.py $A --ctx-opt inf_decode=$v ${EXTRA:-} --out $OUT/bench_$v.json > $OUT/bench_$v.log 2>&1 || { tail -20 $OUT/bench_$v.log; exit 1; }
   python -c "import json;d=json.load(open('$OUT/bench_$v.json'));print('inf_decode $v', d['value'],d['ms_per_step'],d['windows']['mpix_s']);s=d['roofline_isolated']['stages_ms'];print({k:round(v,3) for k,v in s.items() if v>0.02})"

@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=${OUT:-gpurun_out/prog}
 mkdir -p $OUT
-B="--e2e-steps 0 --one-threads 0 --no-cpu-baseline --serial-steps 0"
+B="--full --e2e-steps 0 --one-threads 0 --no-cpu-baseline --serial-steps 0"
 run() {  # name args...
   local name=$1; shift
   timeout -k 10 500 python bench.py $B "$@" --out $OUT/$name.json > $OUT/$name.log 2>&1
