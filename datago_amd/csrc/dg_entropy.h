@@ -895,6 +895,9 @@ DG_HD void schain_range(SyncChain<TAB> &c, const ImageDesc &im, const TAB *tabs,
     c.acc.out = pack_state(0, 0, 0);
     c.phase = 2;
     c.ev = kInf;
+    // its partner's steps still read this chain's tables (schain_step2)
+    c.comp = (im.comp_bits >> (2 * c.r)) & 3u;
+    schain_tables(c, im, tabs, mt, acm);
     if (fresh) {  // a valid window for the frozen steps
       c.pos = 0;
       bw_init(c.b, stream, im.ds_lsw, 0);

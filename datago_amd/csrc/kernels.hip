@@ -590,7 +590,7 @@ __global__ __launch_bounds__(128) void k_huff_sync2(const ImageDesc *__restrict_
     ckv[h] = (q > 0 && active[h] && nck && im.ckpt) ? (DG_GLOBAL Ckpt *)ckpt + im.ckpt_base + (size_t)sv[h] * nck
                                                    : nullptr;
   }
-  SyncChain<HuffTable> A, B;
+  SyncChain<HuffTable> A{}, B{};
   schain_begin(A, im, tabs, scan, mkp, sv[0], im.lead_bits, active[0], ckv[0], mtp, acm);
   schain_begin(B, im, tabs, scan, mkp, sv[1], im.lead_bits, active[1], ckv[1], mtp, acm);
   schain_run2(A, B, im, tabs, scan, mkp, mtp, acm);

@@ -117,7 +117,7 @@ extern "C" int emu_decode_coefs(const uint8_t *data, size_t len, uint32_t sub_bi
     for (uint32_t wg = 0; wg < NW; wg++) {
       const uint32_t s0 = wg * U;
       for (uint32_t t = 0; t < 128; t++) {
-        SyncChain<HuffTable> ch[2];
+        SyncChain<HuffTable> ch[2] = {};
         uint32_t sv[2];
         bool act[2];
         for (int hh = 0; hh < 2; hh++) {
