@@ -273,6 +273,18 @@ def meta_status(metas) -> np.ndarray:
     return raw[:, off:off + 4].copy().view(np.int32).reshape(-1)
 
 
+def payload_array(buf: np.ndarray, m: PayloadMeta) -> np.ndarray:
+    """The HWC pixels of a decoded payload over the bytes of `buf` (a uint8
+    output buffer), without a copy: uint16 samples in native byte order when
+    meta.bit_depth == 16 (context option "png16"), uint8 otherwise."""
+    a = buf[: m.nbytes]
+    sb = 2 if m.bit_depth == 16 else 1
+    if sb == 2:
+        a = a.view(np.uint16)
+    c = int(m.nbytes // (m.width * m.height * sb)) if m.width and m.height else 0
+    return a.reshape(m.height, m.width, c)
+
+
 # Contexts still open at interpreter exit are closed in creation order's
 # reverse by an atexit hook, while the HIP runtime and every thread's buffers
 # still exist (a context may sit in a reference cycle, or in a module global
@@ -313,7 +325,7 @@ class Context:
     def __init__(self, device: int = 0, crop_and_resize: bool = False, default_image_size: int = 0,
                  downsampling_ratio: int = 0, min_aspect_ratio: float = 0.0, max_aspect_ratio: float = 0.0,
                  image_to_rgb8: bool = False, pre_encode_images: bool = False, encode_format: int = 0,
-                 jpeg_quality: int = 92, decode_semantics: int = 0):
+                 jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -328,6 +340,8 @@ class Context:
         self.cfg = cfg
         bt = L.dg_ctx_buckets(h)
         self.buckets = BucketTable(0, 0, 0, 0, _borrowed=bt) if bt else None
+        if png16:  # 16-bit PNGs decode on the GPU (uint16 arrays / tensors); off: DG_ERR_UNSUPPORTED
+            self.set_option("png16", 1)
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None
@@ -387,8 +401,7 @@ class Context:
             if m.is_encoded:  # pre_encode_images: the JPEG bytes
                 res.append((DG_OK, outs[i][: m.nbytes].copy(), m))
                 continue
-            c = int(m.nbytes // (m.width * m.height)) if m.width and m.height else 0
-            res.append((DG_OK, outs[i][: m.nbytes].reshape(m.height, m.width, c), m))
+            res.append((DG_OK, payload_array(outs[i], m), m))
         return res
 
     def decode_one(self, data: bytes, forced_bucket: int = -1, out: Optional[np.ndarray] = None):
@@ -397,7 +410,8 @@ class Context:
         host_register'ed) uint8 buffer of at least output_size bytes.  With
         `out` given the header pass is the library's own: a buffer that turns
         out too small (DG_ERR_SMALL_BUFFER, meta.nbytes = the size needed) is
-        replaced and the call made once more."""
+        replaced and the call made once more.  The array is uint16 (a view of
+        the same bytes) when meta.bit_depth == 16."""
         L = load()
         m = PayloadMeta()
         if out is not None and out.nbytes > 0:
@@ -406,8 +420,7 @@ class Context:
             if st != DG_ERR_SMALL_BUFFER:
                 if st != DG_OK:
                     return st, None, m
-                c = int(m.nbytes // (m.width * m.height)) if m.width and m.height else 0
-                return DG_OK, out[: m.nbytes].reshape(m.height, m.width, c), m
+                return DG_OK, payload_array(out, m), m
             nb = int(m.nbytes)
         else:
             st, nb = self.output_size(data, forced_bucket)
@@ -419,16 +432,15 @@ class Context:
                              ctypes.byref(m))
         if st != DG_OK:
             return st, None, m
-        c = int(m.nbytes // (m.width * m.height)) if m.width and m.height else 0
-        return DG_OK, out[: m.nbytes].reshape(m.height, m.width, c), m
+        return DG_OK, payload_array(out, m), m
 
     # -- host bytes in, HBM out (a training loop consumes the tensors where they are)
     def decode_batch_torch(self, datas: Sequence[bytes], forced: Optional[Sequence[int]] = None):
         """Coded bytes go up once (PCIe carries the compressed stream, ~10x
         less than the decoded pixels); outputs are torch uint8 CUDA tensors
         the kernels write directly (no D2H, no host copy).  Returns
-        [(status, tensor or None, meta)]; HWC tensors, or 1-D bytes when
-        re-encoded."""
+        [(status, tensor or None, meta)]; HWC tensors (uint16 views of the same
+        memory when meta.bit_depth == 16), or 1-D bytes when re-encoded."""
         import torch as _t
         n = len(datas)
         fb = list(forced) if forced else [-1] * n
@@ -458,8 +470,12 @@ class Context:
             elif m.is_encoded:
                 res.append((DG_OK, outs[i][: m.nbytes], m))
             else:
-                c = int(m.nbytes // (m.width * m.height)) if m.width and m.height else 0
-                res.append((DG_OK, outs[i][: m.nbytes].view(m.height, m.width, c), m))
+                t = outs[i][: m.nbytes]
+                sb = 2 if m.bit_depth == 16 else 1
+                if sb == 2:
+                    t = t.view(_t.uint16)
+                c = int(m.nbytes // (m.width * m.height * sb)) if m.width and m.height else 0
+                res.append((DG_OK, t.view(m.height, m.width, c), m))
         del dev_in, host
         return res
 
@@ -512,7 +528,9 @@ class Context:
         """Asynchronous host-in / host-out batch (dg_submit) into caller-owned
         output arrays (reuse them: with dg_host_register'ed memory the outputs
         arrive by DMA, without staging or page faults).  Returns (ticket,
-        metas, keepalive); call wait(ticket) before reading outs or metas."""
+        metas, keepalive); call wait(ticket) before reading outs or metas;
+        payload_array(outs[i], metas[i]) is image i's HWC view (uint16 when
+        meta.bit_depth == 16)."""
         n = len(datas)
         bufs = [ctypes.c_char_p(d) for d in datas]
         srcs = _as_ptr_array([ctypes.cast(b, ctypes.c_void_p).value or 0 for b in bufs])

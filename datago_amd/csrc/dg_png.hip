@@ -5,6 +5,7 @@
 //   k_png_inflate   zlib/DEFLATE -> filtered scanlines, one wave per image
 //   k_png_unfilter  scanline filters -> samples, one wave per 64-row band
 //   k_png_expand    palette / sub-byte gray / tRNS -> 8-bit L, LA, RGB, RGBA
+//   k_png_expand16  16-bit samples: byte order, tRNS key, Adam7 (option "png16")
 //   k_alpha         premultiply / divide by alpha, in place
 //
 // What they restate: png 0.18.0 + fdeflate 0.3.7 as image 0.25.9 drives them
@@ -1349,8 +1350,9 @@ __global__ __launch_bounds__(1024) void k_inf_resolve(ImageDesc *__restrict__ im
 // above (row y-1, x) and above-left (x-1) were produced by lane l-1 at steps
 // t-1 and t-2 and arrive by a lane shuffle; the left pixel is the lane's own
 // previous result.  Lane 0 reads the band's previous row from memory.
-// Samples of up to 4 bytes per filter unit (8-bit L/LA/RGB/RGBA; 1 for
-// palette and sub-byte gray) travel packed in one dword.
+// Samples of up to 4 bytes per filter unit (8-bit L/LA/RGB/RGBA, 16-bit L/LA;
+// 1 for palette and sub-byte gray) travel packed in one dword, the 6- and
+// 8-byte units of 16-bit RGB/RGBA in two (UfUnit).
 __device__ __forceinline__ uint32_t paeth_b(uint32_t a, uint32_t b, uint32_t c) {
   const int p = (int)a + (int)b - (int)c;
   const int pa = abs(p - (int)a), pb = abs(p - (int)b), pc = abs(p - (int)c);
@@ -1360,6 +1362,23 @@ __device__ __forceinline__ uint32_t paeth_b(uint32_t a, uint32_t b, uint32_t c) 
 __device__ __forceinline__ uint32_t shfl_up1(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((threadIdx.x + 63u) & 63u) << 2), (int)v);
 }
+__device__ __forceinline__ uint64_t shfl_up1(uint64_t v) {  // a 6- or 8-byte unit: a pair of shuffles
+  return (uint64_t)shfl_up1((uint32_t)v) | ((uint64_t)shfl_up1((uint32_t)(v >> 32)) << 32);
+}
+// A filter unit in registers: one dword up to 4 bytes, two for the 6- and
+// 8-byte units of 16-bit RGB / RGBA.
+template <uint32_t BPP>
+struct UfUnit {
+  typedef uint32_t T;
+};
+template <>
+struct UfUnit<6> {
+  typedef uint64_t T;
+};
+template <>
+struct UfUnit<8> {
+  typedef uint64_t T;
+};
 
 // The band's raw bytes are staged through LDS in tiles of kUfTile filter
 // units x 64 rows (coalesced loads; the diagonal then reads and writes LDS
@@ -1368,12 +1387,16 @@ __device__ __forceinline__ uint32_t shfl_up1(uint32_t v) {
 // tile k+1.  Each lane takes kUfU units per step (lane l at step t owns units
 // kUfU*(t-l) ..), so one shuffle round trip serves kUfU units.
 // kUfU is a template parameter (option uf_units, 1 or 2; default 2).
+// Units of 6 and 8 bytes always take one unit per step: two of them would
+// need 195 rows of 1028 bytes, more LDS than a CU has, and one per step is
+// exactly the LDS of two 4-byte units (uf_unit_pitch).
 // LDS of one worker: 3 tiles of 64 rows plus 3 previous-band rows, each
 // kUfTile * bpp + 4 bytes (dword misalignment; an odd number of words, so
 // lane rows fall on distinct banks).  Sized for the batch's widest filter
 // unit (dynamic LDS), so batches of 1-3-byte units run more workers per CU.
 __host__ __device__ constexpr uint32_t uf_pitch(uint32_t bpp, uint32_t u) { return 64 * u * bpp + 4; }
 __host__ __device__ constexpr uint32_t uf_smem_bytes(uint32_t bpp, uint32_t u) { return (3 * 64 + 3) * uf_pitch(bpp, u); }
+__host__ __device__ constexpr uint32_t uf_unit_pitch(uint32_t bpp, uint32_t u) { return uf_pitch(bpp, bpp > 4 ? 1 : u); }
 struct UnfilterSmem {
   uint8_t *base;
   uint32_t pitch;
@@ -1381,15 +1404,16 @@ struct UnfilterSmem {
   __device__ __forceinline__ uint8_t *prow(uint32_t k) const { return base + (192 + k % 3) * pitch; }
 };
 
-template <uint32_t BPP>
-__device__ __forceinline__ uint32_t unfilter_unit(uint32_t f, uint32_t rawv, uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t v = 0;
+template <uint32_t BPP, typename T>
+__device__ __forceinline__ T unfilter_unit(uint32_t f, T rawv, T a, T b, T c) {
+  T v = 0;
 #pragma unroll
   for (uint32_t k = 0; k < BPP; k++) {
     const uint32_t sh = 8 * k;
-    const uint32_t ak = (a >> sh) & 0xFFu, bk = (b >> sh) & 0xFFu, ck = (c >> sh) & 0xFFu;
+    const uint32_t ak = (uint32_t)(a >> sh) & 0xFFu, bk = (uint32_t)(b >> sh) & 0xFFu;
+    const uint32_t ck = (uint32_t)(c >> sh) & 0xFFu;
     const uint32_t pr = f == 0 ? 0u : f == 1 ? ak : f == 2 ? bk : f == 3 ? (ak + bk) >> 1 : paeth_b(ak, bk, ck);
-    v |= ((((rawv >> sh) & 0xFFu) + pr) & 0xFFu) << sh;
+    v |= (T)((((uint32_t)(rawv >> sh) & 0xFFu) + pr) & 0xFFu) << sh;
   }
   return v;
 }
@@ -1435,6 +1459,7 @@ template <uint32_t BPP, uint32_t kUfU>
 __device__ void unfilter_band(const UnfilterSmem &sm, ImageDesc &im, uint64_t raw_a, uint64_t unf_a, uint32_t rb,
                               uint32_t us, uint32_t H, uint32_t y0, DG_GLOBAL uint32_t *self,
                               const DG_GLOBAL uint32_t *pred, bool force_timeout) {
+  typedef typename UfUnit<BPP>::T T;
   constexpr uint32_t kUfTile = 64 * kUfU;
   const uint32_t lane = threadIdx.x;
   const uint32_t units = rb / BPP;  // BPP == 1 covers sub-byte samples (filter unit = 1 byte)
@@ -1496,7 +1521,7 @@ __device__ void unfilter_band(const UnfilterSmem &sm, ImageDesc &im, uint64_t ra
     if (ntiles > 1) load_tile(1);
     uint32_t stored = 0;  // tiles [0, stored) are in HBM
     __syncthreads();
-    uint32_t prev[kUfU], prev2 = 0;  // this lane's results of step t-1; last unit of step t-2
+    T prev[kUfU], prev2 = 0;  // this lane's results of step t-1; last unit of step t-2
 #pragma unroll
     for (uint32_t j = 0; j < kUfU; j++) prev[j] = 0;
     const uint32_t nsteps = (units + kUfU - 1) / kUfU + 63;
@@ -1513,7 +1538,7 @@ __device__ void unfilter_band(const UnfilterSmem &sm, ImageDesc &im, uint64_t ra
       }
       const int32_t x0 = (int32_t)(kUfU * t) - (int32_t)(kUfU * lane);
       // this step's raw samples (independent of the shuffles below)
-      uint32_t rawv[kUfU];
+      T rawv[kUfU];
       uint8_t *Tp[kUfU];
 #pragma unroll
       for (uint32_t j = 0; j < kUfU; j++) {
@@ -1521,24 +1546,24 @@ __device__ void unfilter_band(const UnfilterSmem &sm, ImageDesc &im, uint64_t ra
         const bool ok = active && x >= 0 && (uint32_t)x < units;
         const uint32_t xx = ok ? (uint32_t)x : 0u;
         Tp[j] = sm.tile(xx / kUfTile, lane) + myoff + (xx % kUfTile) * BPP;
-        uint32_t v = 0;
+        T v = 0;
 #pragma unroll
-        for (uint32_t k = 0; k < BPP; k++) v |= (uint32_t)Tp[j][k] << (8 * k);
+        for (uint32_t k = 0; k < BPP; k++) v |= (T)Tp[j][k] << (8 * k);
         rawv[j] = v;
       }
       // row above: lane l-1's units of step t-1; above-left of unit 0: its last unit of step t-2
-      uint32_t up[kUfU];
+      T up[kUfU];
 #pragma unroll
       for (uint32_t j = 0; j < kUfU; j++) up[j] = shfl_up1(prev[j]);
-      uint32_t ul0 = shfl_up1(prev2);
+      T ul0 = shfl_up1(prev2);
       if (lane == 0 && x0 >= 0 && (uint32_t)x0 < units) {  // the previous band's last row
 #pragma unroll
         for (uint32_t j = 0; j < kUfU; j++) {
           const uint32_t x = (uint32_t)x0 + j < units ? (uint32_t)x0 + j : (uint32_t)x0;
           const uint8_t *pr = sm.prow(x / kUfTile) + (x % kUfTile) * BPP;
-          uint32_t v = 0;
+          T v = 0;
 #pragma unroll
-          for (uint32_t k = 0; k < BPP; k++) v |= (uint32_t)pr[k] << (8 * k);
+          for (uint32_t k = 0; k < BPP; k++) v |= (T)pr[k] << (8 * k);
           up[j] = v;
         }
         ul0 = 0;
@@ -1546,17 +1571,17 @@ __device__ void unfilter_band(const UnfilterSmem &sm, ImageDesc &im, uint64_t ra
           const uint32_t x = (uint32_t)x0 - 1;
           const uint8_t *pr = sm.prow(x / kUfTile) + (x % kUfTile) * BPP;
 #pragma unroll
-          for (uint32_t k = 0; k < BPP; k++) ul0 |= (uint32_t)pr[k] << (8 * k);
+          for (uint32_t k = 0; k < BPP; k++) ul0 |= (T)pr[k] << (8 * k);
         }
       }
-      uint32_t cur[kUfU];
-      uint32_t left = x0 > 0 ? prev[kUfU - 1] : 0u, ul = x0 > 0 ? ul0 : 0u;
+      T cur[kUfU];
+      T left = x0 > 0 ? prev[kUfU - 1] : (T)0, ul = x0 > 0 ? ul0 : (T)0;
 #pragma unroll
       for (uint32_t j = 0; j < kUfU; j++) {
         const int32_t x = x0 + (int32_t)j;
         const bool ok = active && x >= 0 && (uint32_t)x < units;
-        const uint32_t v = unfilter_unit<BPP>(f, rawv[j], left, up[j], ul);
-        cur[j] = ok ? v : 0u;
+        const T v = unfilter_unit<BPP, T>(f, rawv[j], left, up[j], ul);
+        cur[j] = ok ? v : (T)0;
         if (ok) {
 #pragma unroll
           for (uint32_t k = 0; k < BPP; k++) Tp[j][k] = (uint8_t)(v >> (8 * k));
@@ -1625,11 +1650,13 @@ __global__ __launch_bounds__(64) void k_png_unfilter(ImageDesc *__restrict__ img
     // test switch (debug_flags bit 18): band 1 of every plane times out on its first wait
     const bool force = (dbg & 1u) && band == 1;
     if (!uni(im.status)) {  // (an image whose inflate failed has nothing to unfilter)
-      const UnfilterSmem sm{uf_smem, uf_pitch(pd.bpp <= 4 ? pd.bpp : 4, U)};
+      const UnfilterSmem sm{uf_smem, uf_unit_pitch(pd.bpp, U)};
       switch (pd.bpp) {
         case 1: unfilter_band<1, U>(sm, im, ra, ua, rb, us, H, band * 64, self, pred, force); break;
         case 2: unfilter_band<2, U>(sm, im, ra, ua, rb, us, H, band * 64, self, pred, force); break;
         case 3: unfilter_band<3, U>(sm, im, ra, ua, rb, us, H, band * 64, self, pred, force); break;
+        case 6: unfilter_band<6, 1>(sm, im, ra, ua, rb, us, H, band * 64, self, pred, force); break;  // RGB16
+        case 8: unfilter_band<8, 1>(sm, im, ra, ua, rb, us, H, band * 64, self, pred, force); break;  // RGBA16
         default: unfilter_band<4, U>(sm, im, ra, ua, rb, us, H, band * 64, self, pred, force); break;
       }
     }
@@ -1693,6 +1720,81 @@ __global__ __launch_bounds__(256) void k_png_expand(const ImageDesc *__restrict_
     o[1] = (uint8_t)b;
     o[2] = (uint8_t)c;
     o[3] = (a == pd.trns[0] && b == pd.trns[1] && c == pd.trns[2]) ? 0 : 255;
+  }
+}
+
+// ------------------------------------------------------------ 16-bit samples
+
+// Every 16-bit image takes this pass after the unfilter: big-endian file
+// samples -> native (little-endian) u16, tRNS key -> a 16-bit alpha channel
+// (0 where the whole sample -- all three for RGB -- equals the key, else
+// 65535), Adam7 passes -> their place in the image.  A thread owns two
+// adjacent pixels, so its output is C whole dwords (rows start 16-byte
+// aligned); each dword is one v_perm_b32 over two samples read as they lie in
+// the file.  The last dword of an odd-width row of 1- or 3-channel pixels
+// ends in the row's stride padding.
+__device__ __forceinline__ uint32_t be16_pair(uint32_t s0, uint32_t s1) {
+  // bytes {s0.1, s0.0, s1.1, s1.0}: both samples swapped, s0 in the low half
+  return __builtin_amdgcn_perm(s1, s0, 0x04050001u);
+}
+
+template <uint32_t SPP, bool TRNS>
+__device__ __forceinline__ void expand16_pair(const ImageDesc &im, uint32_t y, uint32_t x0) {
+  constexpr uint32_t C = SPP + (TRNS ? 1u : 0u);
+  const PngDesc &pd = im.png;
+  const uint32_t W = im.width;
+  uint32_t s[2 * C];  // samples of both pixels, bytes as in the file
+#pragma unroll
+  for (uint32_t q = 0; q < 2; q++) {
+    const uint32_t xo = x0 + q;
+    const bool ok = xo < W;
+    const DG_GLOBAL uint16_t *r;
+    uint32_t x = ok ? xo : 0u;
+    if (pd.interlace) {  // as k_png_expand: the pass holding (x, y) and the pixel's place in it
+      const uint32_t xm = x & 7u, ym = y & 7u;
+      const uint32_t p = (ym & 1u) ? 6u : (xm & 1u) ? 5u : (ym & 2u) ? 4u : (xm & 2u) ? 3u : (ym & 4u) ? 2u
+                       : (xm & 4u) ? 1u : 0u;
+      const A7Pass a = png_adam7(W, im.height, SPP * 16u, p);
+      r = gp<const uint16_t>(pd.unf + a.unf_off + (uint64_t)((y - png_a7(p, 1)) / png_a7(p, 3)) * a.us);
+      x = (x - png_a7(p, 0)) / png_a7(p, 2);
+    } else {
+      r = gp<const uint16_t>(pd.unf + (uint64_t)y * pd.ustride);
+    }
+    bool key = TRNS;
+#pragma unroll
+    for (uint32_t k = 0; k < SPP; k++) {
+      const uint32_t v = ok ? (uint32_t)r[(size_t)x * SPP + k] : 0u;
+      s[q * C + k] = v;
+      if (TRNS) key = key && v == (((pd.trns[k] & 0xFFu) << 8) | (pd.trns[k] >> 8));
+    }
+    if (TRNS) s[q * C + SPP] = key ? 0u : 0xFFFFu;
+  }
+  DG_GLOBAL uint32_t *o = gp<uint32_t>(im.pix + (uint64_t)y * im.pix_stride) + (size_t)(x0 / 2u) * C;
+#pragma unroll
+  for (uint32_t k = 0; k < C; k++) o[k] = be16_pair(s[2 * k], s[2 * k + 1]);
+}
+
+__global__ __launch_bounds__(256) void k_png_expand16(const ImageDesc *__restrict__ imgs,
+                                                      const WgItem *__restrict__ list) {
+  const WgItem it = list[blockIdx.x];
+  const ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  const PngDesc &pd = im.png;
+  const uint32_t idx = it.item0 + threadIdx.x;
+  const uint32_t pairs = (im.width + 1u) / 2u;
+  if (idx >= pairs * im.height) return;
+  const uint32_t y = idx / pairs, x0 = 2u * (idx - y * pairs);
+  switch (pd.ctype) {
+    case 0:
+      if (pd.has_trns) expand16_pair<1, true>(im, y, x0);
+      else expand16_pair<1, false>(im, y, x0);
+      break;
+    case 2:
+      if (pd.has_trns) expand16_pair<3, true>(im, y, x0);
+      else expand16_pair<3, false>(im, y, x0);
+      break;
+    case 4: expand16_pair<2, false>(im, y, x0); break;
+    default: expand16_pair<4, false>(im, y, x0); break;
   }
 }
 
@@ -1831,10 +1933,12 @@ static void launch_png_unfilter_t(uint32_t max_per_cu, hipStream_t st, ImageDesc
   static bool attr = false;  // > 64 KiB of dynamic LDS
   if (!attr) {
     (void)hipFuncSetAttribute((const void *)k_png_unfilter<U>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)uf_smem_bytes(4, U));
+                              (int)std::max(uf_smem_bytes(4, U), uf_smem_bytes(8, 1)));
     attr = true;
   }
-  const uint32_t bpp = maxbpp < 1 ? 1u : maxbpp > 4 ? 4u : maxbpp, lds = uf_smem_bytes(bpp, U);
+  // a batch with a 6- or 8-byte unit (16-bit RGB / RGBA) may also hold 4-byte units at U per step
+  const uint32_t bpp = maxbpp < 1 ? 1u : maxbpp > 8 ? 8u : maxbpp;
+  const uint32_t lds = bpp <= 4 ? uf_smem_bytes(bpp, U) : std::max(uf_smem_bytes(4, U), uf_smem_bytes(bpp, 1));
   uint32_t per_cu = std::max<uint32_t>(1u, (160u * 1024u - 64u) / (lds + 64u));  // workers resident per CU
   if (max_per_cu && per_cu > max_per_cu) per_cu = max_per_cu;
   const uint32_t g = std::min(ntasks, ncu * per_cu);
@@ -1852,6 +1956,9 @@ void launch_png_unfilter(hipStream_t st, ImageDesc *imgs, const WgItem *tasks, u
 }
 void launch_png_expand(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   if (nwg) hipLaunchKernelGGL(k_png_expand, dim3(nwg), dim3(256), 0, st, imgs, list);
+}
+void launch_png_expand16(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_png_expand16, dim3(nwg), dim3(256), 0, st, imgs, list);
 }
 void launch_alpha(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, int point) {
   if (nwg) hipLaunchKernelGGL(k_alpha, dim3(nwg), dim3(256), 0, st, imgs, list, point);

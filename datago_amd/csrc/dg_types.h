@@ -133,7 +133,8 @@ constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1;
 // unfiltered (k_png_unfilter, one wave per 64-row band on a diagonal
 // wavefront, consecutive bands pipelined across CUs)
 // and, for palette / sub-byte / tRNS images, expanded to 8-bit L/LA/RGB/RGBA
-// (k_png_expand).
+// (k_png_expand); 16-bit images (option "png16") always take k_png_expand16
+// instead: big-endian -> native u16, tRNS key, Adam7.
 struct PngDesc {
   uint64_t zs;        // contiguous zlib stream
   uint64_t raw;       // inflated scanlines: height x (1 + rowbytes)
@@ -142,7 +143,7 @@ struct PngDesc {
   uint32_t zlen;      // zlib bytes
   uint32_t rowbytes;  // bytes per scanline (without the filter byte)
   uint32_t ustride;   // stride of unf
-  uint32_t bpp;       // filter unit (bytes)
+  uint32_t bpp;       // filter unit (bytes): 1-4, or 6 / 8 for 16-bit RGB / RGBA
   uint32_t ctype, depth, expand, has_trns;
   uint32_t trns[3];   // gray / RGB transparency key
   uint32_t chunk0;    // chunked inflate: first InfChunk of this image
@@ -326,7 +327,10 @@ struct ImageDesc {
   uint32_t crec;            // bit c: component c's plane holds chroma records (dg_plane.h; option "chroma_rec")
   uint32_t copy_mode;       // k_copy: 0 same channels, 1 L->RGB, 2 RGBA->RGB blend over gray,
                             // 3 LA->RGB of a resized LA image (GrayImage over the LA bytes, B3),
-                            // 4 LA->RGB of an unresized LumaA8 (alpha dropped)
+                            // 4 LA->RGB of an unresized LumaA8 (alpha dropped),
+                            // 5 16-bit samples, same channels, 6 16-bit L / LA / RGB / RGBA -> RGB8
+                            // ((v + 128) / 257 per sample, luma replicated, alpha dropped)
+  uint32_t sample_bytes;    // bytes per sample of the decoded image and, unless copy_mode 6, of the output: 1 or 2
   PngDesc png;
   AlphaOp aop[kAlphaPoints];
   EncDesc enc;

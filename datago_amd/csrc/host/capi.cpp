@@ -205,7 +205,7 @@ dg_status dg_probe(const uint8_t *bytes, size_t len, dg_probe_info *out) {
     out->bit_depth = h.depth;
     out->precision = h.depth;
     out->progressive = h.interlace;  // Adam7
-    out->gpu_supported = h.status == dg::PH_OK;
+    out->gpu_supported = h.status == dg::PH_OK;  // the default options: 0 for 16-bit samples (option "png16")
     if (h.status == dg::PH_CORRUPT) {
       dg::set_error(h.why);
       return DG_ERR_CORRUPT;

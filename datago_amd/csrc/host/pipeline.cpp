@@ -489,6 +489,15 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     progressive_ = v != 0;
     return DG_OK;
   }
+  if (k == "png16") {
+    // 16-bit PNGs on the GPU (default off: DG_ERR_UNSUPPORTED, the caller's CPU
+    // decoder takes them).  1: they decode to native-endian u16 samples
+    // (bit_depth 16), or to RGB8 under image_to_rgb8; a 16-bit image that would
+    // need the resize or an encoder stays DG_ERR_UNSUPPORTED.
+    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
+    png16_ = v != 0;
+    return DG_OK;
+  }
   if (k == "prog_lanes") {  // dg_decode_one: progressive batches in flight on the progressive slots; 0: mixed in
     if (v < 0 || v > kProgSlots) return opt_error(k, v, "valid unless v < 0 || v > " + std::to_string(kProgSlots));
     prog_lanes_ = (int)v;
@@ -1383,15 +1392,17 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
   uint32_t W, H, C;
   if (is_png(h, len)) {
     p.fmt = kFmtPng;
-    parse_png_header(h, len, p.png);
+    parse_png_header(h, len, p.png, png16_);
     if (p.png.status != PH_OK) {
       p.status = p.png.status == PH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
       return DG_OK;
     }
     // the decoder's working set (raw + unfiltered + expanded) must stay 32-bit addressable
     const uint64_t raw = p.png.rawlen;
-    if (raw >= (1ull << 31) || (uint64_t)p.png.width * p.png.height * 4ull >= (1ull << 31) ||
+    const uint64_t sb = p.png.depth == 16 ? 2 : 1;  // bytes per expanded sample
+    if (raw >= (1ull << 31) || (uint64_t)p.png.width * p.png.height * 4ull * sb >= (1ull << 31) ||
         p.png.zlen >= (1ull << 28)) {
+      if (sb == 2) p.png.why = "PNG: 16-bit image too large for the GPU path";
       p.status = DG_ERR_UNSUPPORTED;
       return DG_OK;
     }
@@ -1431,7 +1442,8 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     }
   }
   p.channels = (int32_t)C;  // pre-transform (image_processing.rs:349-351)
-  p.bit_depth = 8;
+  const bool deep = p.fmt == kFmtPng && p.png.depth == 16;  // option "png16" (parse_png_header refuses them without)
+  p.bit_depth = deep && !cfg_.image_to_rgb8 ? 16 : 8;       // to_rgb8 (:367-372) leaves Rgb8
   uint32_t ow = W, oh = H;
   if (has_cfg_) {
     int b = forced;
@@ -1449,8 +1461,20 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
   p.out_h = oh;
   p.out_c = cfg_.image_to_rgb8 ? 3 : C;  // convert_to_rgb8 (:163-186)
   if (cfg_.image_to_rgb8) p.channels = 3;  // image_processing.rs:367-372
-  p.out_bytes = (uint64_t)ow * oh * p.out_c;
+  p.out_bytes = (uint64_t)ow * oh * p.out_c * (p.bit_depth == 16 ? 2 : 1);
   p.img_bytes = p.out_bytes;
+  if (deep && has_cfg_ && !(W == ow && H == oh)) {
+    // the reference resizes non-U8 pixel types with image's own f32 Lanczos3
+    // (resize_to_fill), not the fast_image_resize path restated here
+    p.png.why = "PNG: 16-bit resize (only a 16-bit image of its bucket's size decodes on the GPU)";
+    p.status = DG_ERR_UNSUPPORTED;
+    return DG_OK;
+  }
+  if (deep && cfg_.pre_encode_images && !cfg_.image_to_rgb8) {
+    p.png.why = "PNG: 16-bit image to an encoder (the GPU encoders take 8-bit samples)";
+    p.status = DG_ERR_UNSUPPORTED;
+    return DG_OK;
+  }
   if (cfg_.pre_encode_images) {  // image_processing.rs:374-419
     p.encode = true;
     p.enc_png = cfg_.encode_format == 0;
@@ -1597,6 +1621,8 @@ dg_status Context::submit(int n, const uint8_t *const *h_srcs, const uint8_t *co
   size_t hneed = 0, qneed = 0;  // upper bound of the tables this batch adds
   for (int i = 0; i < n; i++) {
     const ImagePlan &p = b.plans[i];
+    // (planning may run on pool threads; dg_last_error is the caller's)
+    if (p.status == DG_ERR_UNSUPPORTED && p.fmt == kFmtPng && p.png.depth == 16) set_error(p.png.why);
     if (p.status || p.fmt != kFmtJpeg) continue;
     hneed += p.hdr.progressive ? p.hdr.tables.size() : 2u * (size_t)p.hdr.ncomp;
     qneed += (size_t)p.hdr.ncomp;
@@ -1711,6 +1737,7 @@ dg_status Context::submit(int n, const uint8_t *const *h_srcs, const uint8_t *co
     if (p.status) continue;
     ImageDesc d;
     memset(&d, 0, sizeof(d));
+    d.sample_bytes = 1;
     Offs o;
     memset(&o, 0, sizeof(o));
     o.late = 0;
@@ -1740,6 +1767,9 @@ dg_status Context::submit(int n, const uint8_t *const *h_srcs, const uint8_t *co
       pd.interlace = (uint32_t)g.interlace;
       pd.rawlen = (uint32_t)g.rawlen;
       pd.expand = g.ctype == 3 || g.depth < 8 || g.has_trns || g.interlace;  // k_png_expand also de-interlaces
+      const bool deep = g.depth == 16;  // always through k_png_expand16 (byte order)
+      if (deep) pd.expand = 1;
+      if (deep) d.sample_bytes = 2;
       o.zs = L.take((size_t)g.zlen + 64, 256);
       // chunk-parallel inflate for streams of at least two chunks (small ones,
       // e.g. masks, inflate serially in one wave)
@@ -1773,7 +1803,11 @@ dg_status Context::submit(int n, const uint8_t *const *h_srcs, const uint8_t *co
       o.raw = L.take((size_t)g.rawlen + 16, 256);
       o.unf = (alias ? LT : L).take(g.interlace ? (size_t)g.unflen + 16 : (size_t)H * pd.ustride, 256);
       o.late |= alias ? 1u : 0u;
-      if (pd.expand) {
+      if (deep) {  // k_png_expand16 writes whole pixel pairs: C dwords each
+        d.pix_stride = (uint32_t)align_up((size_t)((W + 1) / 2) * 4 * C, 16);
+        o.pix = (alias ? LT : L).take((size_t)d.pix_stride * H);
+        o.late |= alias ? 2u : 0u;
+      } else if (pd.expand) {
         d.pix_stride = (uint32_t)align_up((size_t)W * C, 16);
         o.pix = (alias ? LT : L).take((size_t)d.pix_stride * H);
         o.late |= alias ? 2u : 0u;
@@ -1935,7 +1969,7 @@ dg_status Context::submit(int n, const uint8_t *const *h_srcs, const uint8_t *co
     d.out_w = p.out_w;
     d.out_h = p.out_h;
     d.out_c = p.out_c;
-    d.out_stride = p.out_w * p.out_c;
+    d.out_stride = p.out_w * p.out_c * (p.bit_depth == 16 ? 2 : 1);
     // Passes (fast_image_resize semantics, B1): call 1 resizes W x H to the
     // scaled nw x nh, call 2 crops the bucket out of it with a possibly
     // fractional (x.5) offset.  An integral crop offset on an axis is only a
@@ -2078,7 +2112,9 @@ dg_status Context::submit(int n, const uint8_t *const *h_srcs, const uint8_t *co
       d.final_src_c = C;
       d.final_src_stride = (uint32_t)cur_stride;
       o.final_off = (size_t)yoff * cur_stride + (size_t)xoff * C;  // an uncomputed integral crop
-      if (d.out_c == C)
+      if (d.sample_bytes == 2)  // 16-bit PNG (never resized: plan_image): u16 copy, or to_rgb8
+        d.copy_mode = p.bit_depth == 16 ? 5 : 6;
+      else if (d.out_c == C)
         d.copy_mode = 0;
       else if (C == 1)
         d.copy_mode = 1;  // L8 -> RGB8
@@ -2415,7 +2451,9 @@ dg_status Context::submit(int n, const uint8_t *const *h_srcs, const uint8_t *co
         b.lists[L_INF_RES].push_back({I, 0});
         for (uint32_t k = 1; k < d.png.nchunks; k++) b.lists[L_INF_FIND].push_back({d.png.chunk0 + k, 0});
       }
-      if (d.png.expand)
+      if (d.sample_bytes == 2)
+        for (uint32_t it = 0; it < (d.width + 1) / 2 * d.height; it += 256) b.lists[L_EXPAND16].push_back({I, it});
+      else if (d.png.expand)
         for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_EXPAND].push_back({I, it});
     } else {
     if (d.prog) {
@@ -2917,6 +2955,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
                           uf_units_, (uint32_t)uf_per_cu_);
     }
     launch_png_expand(sl.st, dd, lst(L_EXPAND), cnt(L_EXPAND));
+    launch_png_expand16(sl.st, dd, lst(L_EXPAND16), cnt(L_EXPAND16));
   }
   if (next()) return DG_ERR_DEVICE;
   if (!from_fix) {

@@ -43,7 +43,7 @@ struct ImagePlan {
   bool encode = false;     // pre_encode_images: out holds a JPEG / PNG of at most out_bytes
   bool enc_png = false;    // encode_format png (dg_penc.hip)
   bool enc_la_gray = false;  // resized LA: encoded as the GrayImage over its bytes
-  uint64_t img_bytes = 0;  // transformed image bytes (out_w * out_h * out_c)
+  uint64_t img_bytes = 0;  // transformed image bytes (out_w * out_h * out_c, x 2 at bit_depth 16)
 };
 
 // The completion event of one batch (shared with waiters, so a slot recycled
@@ -177,6 +177,7 @@ enum ListId {
   L_DEC,                                                    // IDCT + colour + first H pass (k_band_dec)
   L_RM0, L_RM2,                                             // band H passes on the matrix cores (k_resize_hm)
   L_RVT1, L_RVT3,                                           // V passes on column tiles (k_resize_vt)
+  L_EXPAND16,                                               // 16-bit PNG sample step (k_png_expand16)
   L_COUNT
 };
 static_assert((int)L_COUNT <= 40, "Batch::lists");
@@ -481,6 +482,7 @@ class Context {
   uint32_t dec_strips_ = kDecStripsDefault;  // option "dec_strips"
   bool idct_fused_ = false;             // option "idct_fused" (measured 7x slower k_huff_write: off)
   bool progressive_ = true;             // option "progressive"
+  bool png16_ = false;                  // option "png16": 16-bit PNGs decode on the GPU
   bool prog_serial_ = false;            // option "prog_serial": serial reader for every scan (A/B)
   bool prog_pipe_ = true;               // option "prog_pipe": all scans in one pipelined launch (0: one launch per level)
   int prog_chain_ = 100;                // option "prog_chain": chain dependency groups costing <= this % of the longest scan

@@ -1,9 +1,10 @@
 // png_header.cpp — PNG chunk walk (see png_header.h).
 //
 // Behaviour follows png 0.18.0 as image 0.25.9 drives it (EXPAND): colour
-// types 0/2/3/4/6, depths per the spec table; 16-bit samples and Adam7
-// interlacing are valid but outside the GPU path (PH_UNSUPPORTED: the Rust
-// glue keeps its CPU decode for them).  Chunk CRCs are not verified here
+// types 0/2/3/4/6, depths per the spec table.  16-bit samples are valid but
+// outside the default GPU path (PH_UNSUPPORTED: the Rust glue keeps its CPU
+// decode for them) unless the caller asks for them (context option "png16").
+// Chunk CRCs are not verified here
 // (decoding never depends on them) and, like png's default
 // (ignore_adler32), neither is the zlib Adler-32 trailer.
 #include "png_header.h"
@@ -23,7 +24,7 @@ static void fail(PngHeader &h, int st, const char *why) {
   h.why = why;
 }
 
-void parse_png_header(const uint8_t *d, size_t n, PngHeader &h) {
+void parse_png_header(const uint8_t *d, size_t n, PngHeader &h, bool allow16) {
   h = PngHeader();
   memset(h.pal, 0, sizeof(h.pal));
   for (int i = 0; i < 256; i++) h.pal[i][3] = 255;
@@ -98,7 +99,7 @@ void parse_png_header(const uint8_t *d, size_t n, PngHeader &h) {
   if ((bits + 7) / 8 > 0x7FFFFFF0ull) return fail(h, PH_UNSUPPORTED, "PNG: scanline too long");
   h.rowbytes = (uint32_t)((bits + 7) / 8);
   h.bpp = (int)(((uint64_t)h.spp * dp + 7) / 8);
-  if (dp == 16) return fail(h, PH_UNSUPPORTED, "PNG: 16-bit samples (CPU path)");
+  if (dp == 16 && !allow16) return fail(h, PH_UNSUPPORTED, "PNG: 16-bit samples (CPU path)");
   // Adam7 (PNG spec 8.2): seven sub-images back to back, empty ones absent
   h.rawlen = h.unflen = 0;
   for (uint32_t p = 0; p < (h.interlace ? 7u : 1u); p++) {

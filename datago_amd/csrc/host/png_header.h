@@ -22,7 +22,7 @@ struct PngHeader {
   uint32_t width = 0, height = 0;
   int depth = 0, ctype = 0, interlace = 0;
   int spp = 0;           // samples per pixel in the file (1 gray/palette, 2 LA, 3 RGB, 4 RGBA)
-  int out_c = 0;         // channels after EXPAND: L8 1, La8 2, Rgb8 3, Rgba8 4
+  int out_c = 0;         // channels after EXPAND: L8 1, La8 2, Rgb8 3, Rgba8 4 (the same at depth 16)
   int bpp = 1;           // filter unit in bytes (PNG spec 9.2)
   uint32_t rowbytes = 0; // bytes per unfiltered scanline (without the filter byte)
   uint8_t pal[256][4];   // palette as RGBA (tRNS alpha, 255 default; black past PLTE)
@@ -41,6 +41,9 @@ bool is_png(const uint8_t *d, size_t n);
 std::vector<uint8_t> png_enc_header(uint32_t w, uint32_t h, uint32_t C);
 uint64_t png_enc_bound(uint32_t w, uint32_t h, uint32_t C);
 // Walks every chunk header (reads 8 bytes per chunk plus IHDR/PLTE/tRNS payloads).
-void parse_png_header(const uint8_t *d, size_t n, PngHeader &h);
+// allow16: depth-16 files get their geometry (bpp 2/4/6/8, rowbytes, rawlen,
+// unflen) and PH_OK instead of PH_UNSUPPORTED; out_c then counts 16-bit
+// channels (Luma16 1, LumaA16 2, Rgb16 3, Rgba16 4).
+void parse_png_header(const uint8_t *d, size_t n, PngHeader &h, bool allow16 = false);
 
 }  // namespace dg

@@ -99,6 +99,8 @@ void launch_png_unfilter(hipStream_t st, ImageDesc *imgs, const WgItem *tasks, u
                          uint32_t units, uint32_t max_per_cu);  // max_per_cu: workers per CU cap (0: LDS-bound)
 // 256 pixels per workgroup
 void launch_png_expand(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// 16-bit images: 256 pixel pairs per workgroup (byte swap, tRNS key, Adam7 scatter)
+void launch_png_expand16(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // alpha program at `point` (0 before call 1, 1 between the calls, 2 after call 2): 256 pixels per workgroup
 void launch_alpha(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, int point);
 size_t png_inflate_smem();

@@ -3190,6 +3190,24 @@ __global__ __launch_bounds__(256) void k_copy(const ImageDesc *__restrict__ imgs
     case 2:  // RGBA8 -> RGB8: Pixel::blend over opaque (128,128,128) (image_processing.rs:172-179)
       blend_over_gray(s, d);
       break;
+    case 5: {  // 16-bit image, same channels: native-endian u16 samples, tight rows
+      const DG_GLOBAL uint16_t *s16 =
+          gp<const uint16_t>(im.final_src + (uint64_t)y * im.final_src_stride) + (size_t)x * im.final_src_c;
+      DG_GLOBAL uint16_t *d16 = gp<uint16_t>(im.out) + (size_t)idx * im.out_c;
+      for (uint32_t c = 0; c < im.out_c; c++) d16[c] = s16[c];
+      break;
+    }
+    case 6: {  // 16-bit L / LA / RGB / RGBA -> RGB8 (DynamicImage::to_rgb8): (v + 128) / 257 per sample,
+               // luma replicated, alpha dropped (the gray-background blend is the Rgba8 arm only)
+      const DG_GLOBAL uint16_t *s16 =
+          gp<const uint16_t>(im.final_src + (uint64_t)y * im.final_src_stride) + (size_t)x * im.final_src_c;
+      const bool rgb = im.final_src_c >= 3;
+      const uint32_t r = s16[0], g = rgb ? s16[1] : r, b = rgb ? s16[2] : r;
+      d[0] = (uint8_t)((r + 128u) / 257u);
+      d[1] = (uint8_t)((g + 128u) / 257u);
+      d[2] = (uint8_t)((b + 128u) / 257u);
+      break;
+    }
     default: {  // resized LA: image_to_dyn_image made a GrayImage over the LA bytes
       const uint32_t rb = im.out_w * 2, r = idx / rb, c = idx - r * rb;
       const uint8_t v = gp<const uint8_t>(im.final_src)[(size_t)r * im.final_src_stride + c];

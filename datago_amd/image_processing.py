@@ -87,8 +87,9 @@ class ImageTransformConfig:
 class ARAwareTransform:
     """Bucket table + the device context that applies it."""
 
-    def __init__(self, cfg: ImageTransformConfig, device: int = 0):
+    def __init__(self, cfg: ImageTransformConfig, device: int = 0, png16: bool = False):
         self.cfg = cfg
+        self.png16 = png16  # context option "png16": 16-bit PNGs of a bucket's size decode on the GPU
         self.table = _lib.BucketTable(cfg.default_image_size, cfg.downsampling_ratio, cfg.min_aspect_ratio,
                                       cfg.max_aspect_ratio)
         bl = self.table.buckets()
@@ -111,7 +112,8 @@ class ARAwareTransform:
                                           min_aspect_ratio=c.min_aspect_ratio,
                                           max_aspect_ratio=c.max_aspect_ratio,
                                           image_to_rgb8=enc.img_to_rgb8, pre_encode_images=enc.encode_images,
-                                          encode_format=int(enc.encode_format), jpeg_quality=enc.jpeg_quality)
+                                          encode_format=int(enc.encode_format), jpeg_quality=enc.jpeg_quality,
+                                          png16=self.png16)
         return self._ctx[key]
 
 
@@ -133,7 +135,7 @@ class ImagePayload:
 
     def to_numpy_array(self) -> np.ndarray:
         """structs.rs:154-188 equivalent."""
-        a = np.frombuffer(self.data, np.uint8)
+        a = np.frombuffer(self.data, np.uint16 if self.bit_depth == 16 else np.uint8)  # native-endian u16
         if self.channels == 1:
             return a.reshape(self.height, self.width)
         return a.reshape(self.height, self.width, self.channels)
@@ -146,21 +148,24 @@ class ImagePayload:
 _plain_ctx: Dict[tuple, _lib.Context] = {}
 
 
-def _decode_ctx(device: int, enc: "ImageEncoding") -> _lib.Context:
-    key = (device, enc.img_to_rgb8, enc.encode_images, int(enc.encode_format), enc.jpeg_quality)
+def _decode_ctx(device: int, enc: "ImageEncoding", png16: bool = False) -> _lib.Context:
+    key = (device, enc.img_to_rgb8, enc.encode_images, int(enc.encode_format), enc.jpeg_quality, png16)
     if key not in _plain_ctx:
         _plain_ctx[key] = _lib.Context(device, image_to_rgb8=enc.img_to_rgb8, pre_encode_images=enc.encode_images,
-                                       encode_format=int(enc.encode_format), jpeg_quality=enc.jpeg_quality)
+                                       encode_format=int(enc.encode_format), jpeg_quality=enc.jpeg_quality,
+                                       png16=png16)
     return _plain_ctx[key]
 
 
 def images_to_payloads(datas: List[bytes], img_tfm: Optional[ARAwareTransform], aspect_ratios: List[str],
-                       encoding: ImageEncoding = ImageEncoding(), device: int = 0
+                       encoding: ImageEncoding = ImageEncoding(), device: int = 0, png16: bool = False
                        ) -> List[Tuple[int, Optional[ImagePayload]]]:
     """Batched image_to_payload over coded bytes: one GPU batch.  Returns
     (status, payload) per image; status != 0 means the reference would have
     returned an ImageError (CORRUPT) or the format is outside the GPU path
-    (UNSUPPORTED, the caller's CPU path keeps it)."""
+    (UNSUPPORTED, the caller's CPU path keeps it).  png16 (without a
+    transform; a transform carries its own): 16-bit PNGs decode to
+    bit_depth-16 payloads whose data is native-endian u16."""
     if img_tfm is not None:
         ctx = img_tfm.context(encoding)
         forced = []
@@ -173,7 +178,7 @@ def images_to_payloads(datas: List[bytes], img_tfm: Optional[ARAwareTransform], 
                 raise KeyError("Aspect ratio not found in aspect ratio to size map")  # :334-336
             forced.append(k)
     else:
-        ctx = _decode_ctx(device, encoding)
+        ctx = _decode_ctx(device, encoding, png16)
         forced = [-1] * len(datas)
     out = []
     for st, arr, m in ctx.decode_batch(datas, forced):
@@ -187,17 +192,17 @@ def images_to_payloads(datas: List[bytes], img_tfm: Optional[ARAwareTransform], 
 
 
 def image_to_payload(data: bytes, img_tfm: Optional[ARAwareTransform], aspect_ratio: str = "",
-                     encoding: ImageEncoding = ImageEncoding(), device: int = 0) -> ImagePayload:
+                     encoding: ImageEncoding = ImageEncoding(), device: int = 0, png16: bool = False) -> ImagePayload:
     """image_processing.rs:341-431 for one coded image.  Raises
     ValueError (the reference's ImageError) on undecodable input."""
-    st, p = images_to_payloads([data], img_tfm, [aspect_ratio], encoding, device)[0]
+    st, p = images_to_payloads([data], img_tfm, [aspect_ratio], encoding, device, png16)[0]
     if st != _lib.DG_OK:
         raise ValueError(f"image decode failed: {_lib.STATUS_NAMES.get(st, st)}")
     return p
 
 
 def images_to_tensors(datas: List[bytes], img_tfm: Optional[ARAwareTransform], aspect_ratios: List[str],
-                      encoding: ImageEncoding = ImageEncoding(), device: int = 0):
+                      encoding: ImageEncoding = ImageEncoding(), device: int = 0, png16: bool = False):
     """images_to_payloads for a GPU training loop: the
     payload data stays in HBM as torch uint8 tensors written by the kernels,
     without the D2H copy and the two to three host copies of the Python
@@ -211,7 +216,7 @@ def images_to_tensors(datas: List[bytes], img_tfm: Optional[ARAwareTransform], a
                 raise KeyError("Aspect ratio not found in aspect ratio to size map")  # :334-336
             forced.append(k)
     else:
-        ctx = _decode_ctx(device, encoding)
+        ctx = _decode_ctx(device, encoding, png16)
         forced = [-1] * len(datas)
     return ctx.decode_batch_torch(datas, forced)
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import io
 import math
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 from PIL import Image, ImageDraw
@@ -683,6 +683,18 @@ def make_png(seed: int, w: int, h: int, kind: str = "RGB", **kw) -> bytes:
     else:
         raise ValueError(kind)
     return encode_png(rows, w, h, depth, ctype, bpp, rng, plte=plte, trns=trns, samples=samples, **kw)
+
+
+def encode_png16(px: np.ndarray, ctype: int, rng: np.random.Generator, trns: Optional[Sequence[int]] = None,
+                 **kw) -> bytes:
+    """16-bit PNG (colour type 0 / 2 / 4 / 6) from a uint16 array (h, w, spp):
+    big-endian samples through encode_png, so the array is what a decoder must
+    give back.  trns: the 16-bit key sample(s) of a tRNS chunk (types 0, 2)."""
+    h, w, spp = px.shape
+    assert px.dtype == np.uint16 and spp == {0: 1, 2: 3, 4: 2, 6: 4}[ctype]
+    be = px.astype(">u2").view(np.uint8).reshape(h, w, 2 * spp)
+    key = np.asarray(trns, ">u2").tobytes() if trns is not None else None
+    return encode_png(be.reshape(h, w * 2 * spp), w, h, 16, ctype, 2 * spp, rng, trns=key, samples=be, **kw)
 
 
 def pil_png(arr: np.ndarray, **kw) -> bytes:

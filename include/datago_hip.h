@@ -46,7 +46,9 @@ extern "C" {
 typedef enum dg_status {
   DG_OK = 0,
   DG_ERR_UNSUPPORTED = 1, /* valid image the GPU path does not decode (arithmetic, 12-bit,
-                             CMYK, 16-bit PNG, non-JPEG/PNG...): caller keeps its CPU path */
+                             CMYK, non-JPEG/PNG...; 16-bit PNG unless option "png16" is set,
+                             and then still one that needs the resize or an encoder):
+                             caller keeps its CPU path */
   DG_ERR_CORRUPT = 2,     /* maps to image::ImageError::Decoding: drop the sample */
   DG_ERR_OOM = 3,         /* device or host allocation failed */
   DG_ERR_BAD_BUCKET = 4,  /* forced aspect-ratio key/index not in the table (the reference panics) */
@@ -107,7 +109,7 @@ typedef struct dg_probe_info {
   int32_t format;         /* DG_FMT_* */
   uint32_t width, height;
   int32_t components;     /* 1 (L8) or 3 (RGB8) for JPEG */
-  int32_t bit_depth;      /* bits per channel (8) */
+  int32_t bit_depth;      /* bits per channel (8; 16 for a 16-bit PNG) */
   int32_t h_samp[4], v_samp[4];
   int32_t progressive, arithmetic, precision, restart_interval;
   int32_t gpu_supported;  /* 1 if dg_submit would decode it on the GPU */
@@ -135,7 +137,9 @@ const dg_bucket_table *dg_ctx_buckets(const dg_ctx *ctx);
 
 /* Output metadata, mirrors ImagePayload (structs.rs:52-71).  channels and
  * bit_depth are the decoded image's (pre-transform, image_processing.rs:347-351)
- * unless image_to_rgb8 converted it (then 3 / 8). */
+ * unless image_to_rgb8 converted it (then 3 / 8).  bit_depth 16 (option
+ * "png16"): the output is native-endian uint16 samples, HWC and tightly packed,
+ * nbytes = 2 * width * height * channels (DynamicImage::into_bytes). */
 typedef struct dg_payload_meta {
   uint32_t original_width, original_height;
   uint32_t width, height;
@@ -251,6 +255,15 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 DG_ERR_UNSUPPORTED those failures return)
  *   "progressive" 1 = decode progressive JPEGs on the GPU (default 1; 0: DG_ERR_UNSUPPORTED, the
  *                 caller's CPU decoder takes them)
+ *   "png16"       1 = decode 16-bit PNGs on the GPU (default 0: DG_ERR_UNSUPPORTED, as dg_probe's
+ *                 gpu_supported reports, which describes the default options).  Colour types 0/2/4/6
+ *                 become Luma16 / Rgb16 / LumaA16 / Rgba16 (a tRNS key adds a 16-bit alpha, 0 or
+ *                 65535), Adam7 included; meta.bit_depth 16, samples native-endian uint16.  With
+ *                 image_to_rgb8 every sample is reduced as (v + 128) / 257, luma replicated, alpha
+ *                 dropped (meta 3 / 8), and the encoders take the result.  Still DG_ERR_UNSUPPORTED
+ *                 (dg_last_error says which): a 16-bit image whose size differs from its bucket's
+ *                 (the reference resizes it with image's own f32 Lanczos3), and one that would reach
+ *                 an encoder as 16-bit (pre_encode_images without image_to_rgb8)
  *   "prog_split"  1 = progressive members of a dg_submit run in the progressive aggregate (default 1,
  *                 see dg_wait_ready); 0 = in the submission's own batch
  *   "prog_batch"  progressive aggregate: launched once it holds this many images (default 2048)
