@@ -31,6 +31,7 @@ SOURCES = [
     ("host/wds.cpp", False),
     ("host/png_header.cpp", False),
     ("host/pipeline.cpp", False),
+    ("host/submit.cpp", False),
     ("host/capi.cpp", False),
     ("host/jpeg_header.cpp", False),
     ("host/buckets.cpp", False),

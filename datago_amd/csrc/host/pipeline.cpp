@@ -1,4 +1,5 @@
-// pipeline.cpp — batch planner + runtime for the decode/bucket-resize stage.
+// pipeline.cpp — batch runtime for the decode/bucket-resize stage: context
+// lifecycle, options, statistics, device memory, launch and finish.
 //
 // Host work per image is header-only (parse + bucket + buffer layout); all
 // pixel and coefficient arithmetic runs in kernels.hip.  A batch is laid out
@@ -6,12 +7,15 @@
 // one H2D copy, and every kernel of the batch is launched on the context's
 // stream back to back.  The reference equivalent is one tokio task per sample
 // (worker_files.rs:32-72 -> image_processing.rs:341-431).
-#include "pipeline.h"
+//
+// The batch planner (Context::submit and its phases: the buffer layout, the
+// pass plan with band_dec_mode and the other kernel choices, the workgroup
+// lists) is in submit.cpp.
+#include "pipeline_util.h"
 
 #include <string.h>
 
 #include <algorithm>
-#include <time.h>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -26,53 +30,10 @@ namespace dg {
 thread_local std::string g_last_error;
 void set_error(const std::string &s) { g_last_error = s; }
 
-#define HIPCHK(x)                                                                          \
-  do {                                                                                     \
-    hipError_t e_ = (x);                                                                   \
-    if (e_ != hipSuccess) {                                                                \
-      set_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x);          \
-      return DG_ERR_DEVICE;                                                                \
-    }                                                                                      \
-  } while (0)
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-static double thread_cpu_us() {
-  timespec ts;
-  clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts);
-  return (double)ts.tv_sec * 1e6 + (double)ts.tv_nsec * 1e-3;
-}
-
 // Boundary-repair rounds (finish()) before a batch is declared unsettled.
 static constexpr int kMaxResyncRounds = 64;
-// submit(): the batch does not fit the device (budget or allocation); the
-// caller splits it (submit_split).  Never returned through the C ABI.
-static constexpr dg_status kNeedSplit = (dg_status)15;  // (inside the enum's value range)
 
-// 64-row unfilter bands of pass p of a PNG (the image itself when not
-// interlaced); k_png_unfilter numbers its progress flags the same way.
-static uint32_t png_pass_bands(const ImageDesc &d, uint32_t p) {
-  if (!d.png.interlace) return p == 0 ? (d.height + 63) / 64 : 0u;
-  uint32_t pw, ph;
-  png_adam7_pass(d.width, d.height, p, pw, ph);
-  return pw && ph ? (ph + 63) / 64 : 0u;
-}
-static uint32_t png_bands(const ImageDesc &d) {
-  uint32_t n = 0;
-  for (uint32_t p = 0; p < 7; p++) n += png_pass_bands(d, p);
-  return n;
-}
-
-// Host-side copies of a finished batch's outputs (pinned staging -> the
-// caller's buffers, ~3 MB per 1024-bucket image): split into 1 MiB pieces
-// and spread over up to `nthreads` threads -- one thread's memcpy (~6-8 GB/s)
-// was the limit of the host-in/host-out path, not PCIe.
-struct CopyJob {
-  void *dst;
-  const void *src;
-  size_t n;
-};
-static void parallel_copy(const std::vector<CopyJob> &jobs, int nthreads) {
+void parallel_copy(const std::vector<CopyJob> &jobs, int nthreads) {
   constexpr size_t kPiece = 1 << 20;
   std::vector<CopyJob> pieces;
   size_t total = 0;
@@ -309,65 +270,6 @@ dg_status Context::sync_all() {
   return DG_OK;
 }
 
-// H pass kernel choice.  The band kernel stages the source pixels of
-// kHBandCols consecutive outputs in LDS: at most 255 * scale + 2 * support
-// (+ window rounding, 8-pixel alignment and ksize slack) pixels, which must
-// fit kHSegPx.  Wider segments (extreme downscales) use the direct kernel;
-// the first pass of a colour JPEG in the band kernel upsamples and converts
-// colour in its fill.
-static double h_pass_span(const ResizePass &ps) {
-  const double scale = (ps.in1 - ps.in0) / (double)ps.out_size;
-  const double fs = scale > 1.0 ? scale : 1.0;
-  return std::ceil((kHBandCols - 1) * scale + 6.0 * fs) + 2.0 + 8.0 + (double)ps.ksize + 8.0;
-}
-static uint32_t h_pass_mode(const ResizePass &ps, bool colour_source) {
-  if (h_pass_span(ps) > (double)kHSegPx) return kHDirect;
-  return colour_source ? kHFused : 0u;
-}
-// k_resize_hv takes the first H and V passes of a colour JPEG together when
-// its smaller segment and ring fit them and the H taps are in the <= 16 class
-static bool hv_fusable(const ResizePass &h, const ResizePass &v) {
-  return h.kind == 1 && (h.mode & kHFused) && !(h.mode & kHDirect) && v.kind == 2 && h.C == 3 && h.row0 == 0 &&
-         v.row0 == 0 &&
-         h.ksize + 1 <= 16 && v.ksize <= kHVTapsMax && h_pass_span(h) <= (double)kHVSegPx;
-}
-
-// k_band_dec takes pass[0] of a JPEG when its sampling is one the fused fill
-// knows (gray; 4:4:4, 4:2:2, 4:2:0 with luma at the maximum factors) and its
-// segments fit: the 128-column tile's source segment (plus the 16-pixel
-// alignment) in the class's LDS, every 16-column MFMA subtile's window in the
-// class's K steps (320-pixel class: one 64-wide step, downscales up to ~2x;
-// 640-pixel class: two).  Returns the mode bits (0: not eligible).
-static uint32_t band_dec_mode(const ImageDesc &d, const ResizePass &ps) {
-  if (ps.kind != 1 || (ps.mode & (kHDirect | kHVFused)) || d.idct_fused) return 0;
-  if (d.ncomp == 3) {
-    if (!(ps.mode & kHFused)) return 0;
-    if (d.ch[0] != d.hmax || d.cv[0] != d.vmax || d.ch[1] != d.ch[2] || d.cv[1] != d.cv[2]) return 0;
-    if (d.hmax % d.ch[1] || d.vmax % d.cv[1]) return 0;
-    const uint32_t hr = d.hmax / d.ch[1], vr = d.vmax / d.cv[1];
-    if (hr > 2 || vr > 2 || (hr == 1 && vr == 2)) return 0;
-  } else if (d.ncomp != 1) {
-    return 0;
-  }
-  const double scale = (ps.in1 - ps.in0) / (double)ps.out_size;
-  const double window = 15.0 + std::ceil(15.0 * scale) + (double)ps.ksize + 2.0;  // a subtile's K range
-  const double span = h_pass_span(ps) + 16.0;
-  if (span <= (double)kDecSeg0 && window <= 64.0) return kHDecode;  // one K step
-  if (span <= (double)kDecSeg1 && window <= 128.0) return kHDecode | kHDecWide;
-  return 0;
-}
-
-// k_resize_hm takes a band H pass when every 16-column subtile's window fits
-// one or two 64-wide K steps and the 16-aligned segment fits kHSegPx: returns
-// the K steps (0: the VALU band kernel runs it).
-static uint32_t h_mfma_steps(const ResizePass &ps) {
-  if (ps.kind != 1 || (ps.mode & (kHDirect | kHVFused | kHDecode)) || ps.C < 1 || ps.C > 4) return 0;
-  if (h_pass_span(ps) + 8.0 > (double)kHSegPx) return 0;
-  const double scale = (ps.in1 - ps.in0) / (double)ps.out_size;
-  const double window = 15.0 + std::ceil(15.0 * scale) + (double)ps.ksize + 2.0;
-  return window <= 64.0 ? 1u : (window <= 128.0 ? 2u : 0u);
-}
-
 // A rejected option names itself, the value and the accepted range in
 // dg_last_error (the range as the condition that rejects it).
 static dg_status opt_error(const std::string &k, int64_t v, const std::string &why) {
@@ -427,13 +329,7 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     for (const Slot &o : slots_)
       if (o.batch && !o.batch->done && o.batch->uses_ccache) return opt_error(k, v, "not while a batch in flight uses the table cache");  // not while tables are in use
     ccache_cap_ = (size_t)v << 20;
-    ccache_index_clear();
-    ccache_.clear();
-    ccache_off_ = 0;
-    ccache_full_ = false;
-    if (d_ccache_.p) hipFree(d_ccache_.p);
-    d_ccache_.p = nullptr;
-    d_ccache_.cap = 0;
+    ccache_clear(true);
     return DG_OK;
   }
   if (k == "entropy_prio") {  // wave issue priority (s_setprio) of the entropy kernels, 0-3
@@ -1008,11 +904,21 @@ void Context::ccache_maybe_reset(Slot &self) {
     if (&o == &self || !o.batch || o.batch->done || !o.batch->uses_ccache) continue;
     if (finish(o)) return;  // keep the arena as it is; the next batch tries again
   }
+  ccache_clear(false);
+  stat_ccache_resets_++;
+}
+
+// Forget every entry; free_arena: give the device arena back too (the next lookup allocates it again).
+void Context::ccache_clear(bool free_arena) {
   ccache_index_clear();
   ccache_.clear();
   ccache_off_ = 0;
   ccache_full_ = false;
-  stat_ccache_resets_++;
+  if (free_arena && d_ccache_.p) {
+    hipFree(d_ccache_.p);
+    d_ccache_.p = nullptr;
+    d_ccache_.cap = 0;
+  }
 }
 
 void Context::ccache_index_clear() { ccache_slot_.assign((size_t)1 << kCIdxBits, -1); }
@@ -1277,8 +1183,7 @@ dg_status Context::ensure_pinned(PinBuf &b, size_t bytes, hipStream_t user, bool
 // and it serialised the aggregates).  Only a single batch that alone needs
 // more than kPoolMax tables sends its overflow images back as
 // DG_ERR_UNSUPPORTED (the caller's CPU path), never as CORRUPT.
-static constexpr size_t kPoolKeep = 16384;
-static constexpr size_t kPoolMax = 65535;
+// (kPoolKeep and kPoolMax are in pipeline_util.h: the planner checks them too)
 
 dg_status Context::flush_pools() {
   const int next = (pool_gen_ + 1) % kPoolGens;
@@ -1498,1224 +1403,6 @@ dg_status Context::output_size(const uint8_t *bytes, size_t len, int32_t forced,
   *nbytes = p.out_bytes;
   if (p.status) set_error(p.fmt == kFmtPng ? p.png.why : (p.hdr.why ? p.hdr.why : "unsupported"));
   return (dg_status)p.status;
-}
-
-namespace {
-struct Layout {
-  size_t off = 0;
-  size_t take(size_t bytes, size_t align = 256) {
-    off = align_up(off, align);
-    size_t o = off;
-    off += bytes;
-    return o;
-  }
-};
-}  // namespace
-
-dg_status Context::submit(int n, const uint8_t *const *h_srcs, const uint8_t *const *d_srcs, const size_t *lens,
-                          const int32_t *forced, uint8_t *const *outs, const uint64_t *caps,
-                          dg_payload_meta *metas, bool host_io, uint64_t *ticket, dg_payload_meta *const *mptrs,
-                          int force_slot, bool defer_meta) {
-  const auto wait_t0 = std::chrono::steady_clock::now();
-  std::unique_lock<std::mutex> lk(mu_);
-  if (n < 0 || (n > 0 && (!h_srcs || !lens || !outs || !caps || (!metas && !mptrs)))) {
-    set_error("null argument");
-    return DG_ERR_INVALID;
-  }
-  HIPCHK(hipSetDevice(device_));
-  Slot &sl = slots_[force_slot >= 0 ? force_slot : pick_slot()];
-  if (dg_status st = slot_streams(sl)) return st;
-  // This slot's previous batch must complete first.  Its GPU work is waited
-  // for without the context lock: a progressive slot's batch can run ~1 s,
-  // and every other dg_submit / dg_wait / dg_poll of the context would stall
-  // behind it.  Re-checked after relocking: another thread may
-  // have finished that batch, or queued one of its own on the slot.
-  while (sl.batch && !sl.batch->done) {
-    if (hipEventQuery(sl.batch->fin->e) == hipErrorNotReady) {
-      std::shared_ptr<BatchEvent> fin = sl.batch->fin;
-      lk.unlock();
-      const hipError_t e = hipEventSynchronize(fin->e);
-      lk.lock();
-      if (e != hipSuccess) {
-        set_error(std::string("HIP error: ") + hipGetErrorString(e) + " waiting for a slot's batch");
-        return DG_ERR_DEVICE;
-      }
-      continue;
-    }
-    dg_status st = finish(sl);
-    if (st) return st;
-  }
-  // context lock + the slot's previous batch (stat "host_us_slotwait")
-  host_us_[7] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - wait_t0).count();
-  std::unique_ptr<Batch> bp(new Batch());
-  Batch &b = *bp;
-  b.ticket = next_ticket_++;
-  b.fin = std::make_shared<BatchEvent>();
-  HIPCHK(hipEventCreateWithFlags(&b.fin->e, hipEventDisableTiming));
-  b.n = n;
-  b.host_io = host_io;
-  b.mptr.resize(n);
-  for (int i = 0; i < n; i++) b.mptr[i] = mptrs ? mptrs[i] : &metas[i];
-  if (defer_meta) {
-    // A progressive aggregate's members: the callers' metas keep reading
-    // DG_ERR_NOT_READY until finish() publishes the batch's own copies
-    // (dg_wait_ready's contract; the GPU is still decoding while planning
-    // fills in status and dimensions).
-    b.pub = b.mptr;
-    b.local_meta.assign(n, dg_payload_meta{});
-    for (int i = 0; i < n; i++) b.mptr[i] = &b.local_meta[i];
-  }
-  b.plans.resize(n);
-  b.desc_of.assign(n, -1);
-  // host time per submit phase: wall ("host_us_<phase>") and this thread's CPU
-  // time ("host_cpu_us_<phase>"); wall well above CPU = blocking (allocation,
-  // copies, driver locks), not planning work
-  auto phase_t0 = std::chrono::steady_clock::now();
-  double cpu_t0 = thread_cpu_us();
-  auto phase = [&](int k) {
-    const auto now = std::chrono::steady_clock::now();
-    const double c = thread_cpu_us();
-    host_us_[k] += std::chrono::duration<double, std::micro>(now - phase_t0).count();
-    host_cpu_us_[k] += c - cpu_t0;
-    phase_t0 = now;
-    cpu_t0 = c;
-  };
-  // ---- 1. plan every image (host, header only; on the planning workers)
-  auto plan_one = [&](int i) {
-    ImagePlan &p = b.plans[i];
-    plan_image(h_srcs[i], lens[i], forced ? forced[i] : -1, p);
-    dg_payload_meta &m = *b.mptr[i];
-    memset(&m, 0, sizeof(m));
-    m.status = p.status;
-    m.bucket = p.bucket;
-    if (p.fmt == kFmtJpeg && p.hdr.status == JH_OK) {
-      m.original_width = p.hdr.width;
-      m.original_height = p.hdr.height;
-    } else if (p.fmt == kFmtPng && p.png.status == PH_OK) {
-      m.original_width = p.png.width;
-      m.original_height = p.png.height;
-    }
-    m.width = p.out_w;
-    m.height = p.out_h;
-    m.channels = p.channels;
-    m.bit_depth = p.bit_depth;
-    m.is_encoded = p.encode ? 1 : 0;
-    m.nbytes = p.out_bytes;
-    if (p.status == DG_OK && caps[i] < p.out_bytes) {
-      p.status = DG_ERR_SMALL_BUFFER;
-      m.status = DG_ERR_SMALL_BUFFER;
-    }
-    if (p.status == DG_OK && !outs[i]) {
-      p.status = DG_ERR_INVALID;
-      m.status = DG_ERR_INVALID;
-    }
-  };
-  if (plan_threads_ > 1 && n >= 2 * kPlanGrain) {
-    if (!plan_pool_ || plan_pool_->threads() != plan_threads_) plan_pool_.reset(new HostPool(plan_threads_));
-    plan_pool_->run(n, kPlanGrain, plan_one);
-  } else {
-    for (int i = 0; i < n; i++) plan_one(i);
-  }
-  phase(0);
-  // ---- 2. table pools
-  size_t hneed = 0, qneed = 0;  // upper bound of the tables this batch adds
-  for (int i = 0; i < n; i++) {
-    const ImagePlan &p = b.plans[i];
-    // (planning may run on pool threads; dg_last_error is the caller's)
-    if (p.status == DG_ERR_UNSUPPORTED && p.fmt == kFmtPng && p.png.depth == 16) set_error(p.png.why);
-    if (p.status || p.fmt != kFmtJpeg) continue;
-    hneed += p.hdr.progressive ? p.hdr.tables.size() : 2u * (size_t)p.hdr.ncomp;
-    qneed += (size_t)p.hdr.ncomp;
-  }
-  if (hpool_.size() > kPoolKeep || qpool_.size() > kPoolKeep ||
-      (hpool_.size() && hpool_.size() + hneed > kPoolMax) || (qpool_.size() && qpool_.size() + qneed > kPoolMax)) {
-    dg_status st = flush_pools();
-    if (st) return st;
-  }
-  for (int i = 0; i < n; i++) {
-    ImagePlan &p = b.plans[i];
-    if (p.status || p.fmt != kFmtJpeg) continue;
-    int worst = 0;  // -1: a table that does not build (corrupt), -2: pools full for this batch
-    auto use = [&](int idx) { worst = std::min(worst, idx); };
-    if (p.hdr.progressive) {  // the tables each scan uses
-      for (const HuffSpec &t : p.hdr.tables) use(pool_huff(t));
-      for (int c = 0; c < p.hdr.ncomp; c++) use(pool_quant(p.hdr.q[p.hdr.comp[c].tq]));
-    } else {
-      for (int c = 0; c < p.hdr.ncomp; c++) {
-        use(pool_huff(p.hdr.dc[p.hdr.comp[c].td]));
-        use(pool_huff(p.hdr.ac[p.hdr.comp[c].ta]));
-        use(pool_quant(p.hdr.q[p.hdr.comp[c].tq]));
-      }
-    }
-    if (worst == -2) {
-      p.status = DG_ERR_UNSUPPORTED;
-      b.mptr[i]->status = DG_ERR_UNSUPPORTED;
-    } else if (worst < 0) {
-      p.status = DG_ERR_CORRUPT;
-      b.mptr[i]->status = DG_ERR_CORRUPT;
-    }
-  }
-  dg_status st = upload_pools();
-  if (st) return st;
-  b.pool_gen = pool_gen_;
-  b.hp = (const HuffTable *)d_hpool_[pool_gen_].p;
-  b.qp = (const QuantTable *)d_qpool_[pool_gen_].p;
-
-  phase(1);
-  // Lanczos table cache: entries this submit creates are dropped again if it
-  // returns before its batch is installed (budget split, allocation failure)
-  ccache_maybe_reset(sl);
-  struct CacheRoll {
-    Context *c;
-    size_t n0, off0;
-    bool armed = true;
-    ~CacheRoll() {
-      if (armed) c->ccache_rollback(n0, off0);
-    }
-  } croll{this, ccache_.size(), ccache_off_};
-  // ---- 3. layout
-  // Subsequence size: the entropy kernels are latency-bound, so they want as
-  // many lanes as the chip can keep resident, but every subsequence costs a
-  // sync re-decode.  Measured on MI355X (profiles/r01/sweep_v4): 2048 bits
-  // below 64 MiB of coded data (configs[2]'s 1,024 WebDataset members, ~25
-  // MiB: 39.9 vs 38.5 Gpx/s with 4096, profiles/r04/wds_sub2); from 64 MiB
-  // option "sub_auto"
-  // (round 4: 8192, profiles/r04/ab -- the chip stays full with half the
-  // lanes once the write pass no longer decodes, and the 6 kbit lead-in of a
-  // 4:2:0 range costs 75% instead of 150% of its bits).
-  // Small batches (dg_decode_one's few images, option "small_coded" bytes of
-  // coded data) are latency-bound: a lane's chain of lead-in + range bits is
-  // the batch's k_huff_sync time (0.87 ms of a ~3 ms coalesced batch in the
-  // decode_one trace, profiles/r04/one_trace), so they take short ranges and
-  // lead-ins ("sub_small", "lead_small") at the cost of more total decode.
-  uint32_t sub_bits = sub_bits_;
-  bool small = false;
-  if (!sub_bits) {
-    uint64_t coded = 0;
-    for (int i = 0; i < n; i++)
-      if (!b.plans[i].status && b.plans[i].fmt == kFmtJpeg && !b.plans[i].hdr.progressive)
-        coded += b.plans[i].hdr.scan_end - b.plans[i].hdr.scan_off;
-    small = coded < small_coded_;
-    sub_bits = coded >= (64ull << 20) ? sub_auto_ : small ? sub_small_ : 2048u;
-  }
-  last_sub_bits_ = sub_bits;
-  Layout L;        // scratch arena
-  Layout CO;       // coefficient arena (zero-filled per batch)
-  Layout IN;       // input arena (host path)
-  // The chunk-parallel inflate's entries (CH, 2 bytes per output byte, most
-  // of a PNG batch's memory) are dead once k_inf_resolve has turned them into
-  // raw bytes, before anything writes the buffers of the unfilter / expand /
-  // resize stages (LT).  Both regions are laid out from 0 and placed at the
-  // same offset of the scratch arena (option "png_alias", default on).
-  Layout LT, CH;
-  const bool alias = png_alias_;
-  std::vector<size_t> in_off(n, 0);
-  size_t out_total = 0;
-  uint64_t ckpt_total = 0;  // checkpoint records of the batch (per-image sub_bits)
-  b.out_dev_off.assign(n, 0);
-  b.out_direct.assign(n, 0);
-  uint32_t sub_base = 0;
-  b.descs.reserve(n);
-  // first pass: sizes only (pointers are patched after allocation)
-  struct Offs {
-    size_t coef, ccnt, plane[3], pix, pass_dst[kStages], pass_coef[kStages], pass_bounds[kStages], pass_srcoff[kStages];
-    int pass_cache[kStages];    // Lanczos table cache entry of the pass (-1: tables in the scratch arena)
-    bool pass_hit[kStages];     // ... already computed (no k_coeffs item)
-    size_t final_off, tmp, out, ds, mk, chunk, stage;
-    size_t zs, raw, unf, pal;
-    size_t tout, ecoef, ebits, ewords, hdr, eaux;  // JPEG / PNG re-encode
-    // alpha programs: buffer = dst of pass `stage` (-1: the decoded image), byte offset
-    int aop_stage[kAlphaPoints];
-    size_t aop_off[kAlphaPoints];
-    // offsets taken from the late region (LT): bit 0 unf, 1 pix, 2 out, 3 + s pass_dst[s]
-    uint32_t late = 0;
-    int img = -1;
-  };
-  std::vector<Offs> offs;
-  for (int i = 0; i < n; i++) {
-    ImagePlan &p = b.plans[i];
-    if (p.status) continue;
-    ImageDesc d;
-    memset(&d, 0, sizeof(d));
-    d.sample_bytes = 1;
-    Offs o;
-    memset(&o, 0, sizeof(o));
-    o.late = 0;
-    o.img = i;
-    for (int s_ = 0; s_ < kStages; s_++) o.pass_cache[s_] = -1;
-    uint32_t W, H, C;
-    size_t cur_stride;
-    bool colour = false;  // the source is the YCbCr planes of a colour JPEG
-    if (p.fmt == kFmtPng) {
-      const PngHeader &g = p.png;
-      W = g.width;
-      H = g.height;
-      C = (uint32_t)g.out_c;
-      d.fmt = kFmtPng;
-      d.width = W;
-      d.height = H;
-      d.dec_c = (uint8_t)C;
-      PngDesc &pd = d.png;
-      pd.zlen = (uint32_t)g.zlen;
-      pd.rowbytes = g.rowbytes;
-      pd.ustride = (uint32_t)align_up(g.rowbytes, 16);
-      pd.bpp = (uint32_t)g.bpp;
-      pd.ctype = (uint32_t)g.ctype;
-      pd.depth = (uint32_t)g.depth;
-      pd.has_trns = (uint32_t)g.has_trns;
-      for (int k = 0; k < 3; k++) pd.trns[k] = g.trns[k];
-      pd.interlace = (uint32_t)g.interlace;
-      pd.rawlen = (uint32_t)g.rawlen;
-      pd.expand = g.ctype == 3 || g.depth < 8 || g.has_trns || g.interlace;  // k_png_expand also de-interlaces
-      const bool deep = g.depth == 16;  // always through k_png_expand16 (byte order)
-      if (deep) pd.expand = 1;
-      if (deep) d.sample_bytes = 2;
-      o.zs = L.take((size_t)g.zlen + 64, 256);
-      // chunk-parallel inflate for streams of at least two chunks (small ones,
-      // e.g. masks, inflate serially in one wave)
-      {
-        const uint64_t want = g.rawlen;
-        const uint32_t span = inf_chunk_;
-        const uint32_t nch = (uint32_t)((g.zlen + span - 1) / span);
-        if (nch >= 2 && !chunked_off_) {
-          pd.chunk0 = (uint32_t)b.ichunks.size();
-          pd.nchunks = nch;
-          // entries per chunk: inf_cap / 10 times the image's average expansion of a span (+64 Ki), at
-          // most the whole image; a chunk that needs more sends the image to the serial kernel.  The
-          // entries (2 bytes per output byte) are most of a PNG batch's device memory: 3x made them
-          // 6x the raw image
-          const double ratio = (double)want / (double)g.zlen;
-          const uint64_t cap = std::min<uint64_t>(want, (uint64_t)(0.1 * inf_cap_ * ratio * span) + inf_pad_);
-          for (uint32_t k = 0; k < nch; k++) {
-            InfChunk c;
-            memset(&c, 0, sizeof(c));
-            c.image = (uint32_t)b.descs.size();
-            c.idx = k;
-            c.span = span;
-            c.cap = (uint32_t)cap;
-            c.start = k == 0 ? 16u : kInfNone;  // chunk 0: first block after the 2-byte zlib header
-            c.out = (alias ? CH : L).take(cap * 2, 256);  // offsets: made absolute below
-            c.tab = (alias ? CH : L).take(kInfTabBytes, 256);
-            b.ichunks.push_back(c);
-          }
-        }
-      }
-      o.raw = L.take((size_t)g.rawlen + 16, 256);
-      o.unf = (alias ? LT : L).take(g.interlace ? (size_t)g.unflen + 16 : (size_t)H * pd.ustride, 256);
-      o.late |= alias ? 1u : 0u;
-      if (deep) {  // k_png_expand16 writes whole pixel pairs: C dwords each
-        d.pix_stride = (uint32_t)align_up((size_t)((W + 1) / 2) * 4 * C, 16);
-        o.pix = (alias ? LT : L).take((size_t)d.pix_stride * H);
-        o.late |= alias ? 2u : 0u;
-      } else if (pd.expand) {
-        d.pix_stride = (uint32_t)align_up((size_t)W * C, 16);
-        o.pix = (alias ? LT : L).take((size_t)d.pix_stride * H);
-        o.late |= alias ? 2u : 0u;
-      } else {
-        d.pix_stride = pd.ustride;
-      }
-      if (g.ctype == 3) {
-        o.pal = b.blob.size();
-        b.blob.insert(b.blob.end(), &g.pal[0][0], &g.pal[0][0] + 1024);
-      }
-      if (host_io) in_off[i] = IN.take(lens[i] + 16, 16);
-      cur_stride = d.pix_stride;
-      b.any_png = true;
-    } else {
-    const JpegHeader &h = p.hdr;
-    W = h.width;
-    H = h.height;
-    d.width = W;
-    d.height = H;
-    d.ncomp = (uint8_t)h.ncomp;
-    d.colorspace = (uint8_t)h.colorspace;
-    d.sem = (uint16_t)decode_sem_;
-    d.ckpt = ckpt_ ? 1u : 0u;
-    d.dec_c = h.ncomp == 1 ? 1 : 3;
-    d.hmax = (uint32_t)h.hmax;
-    d.vmax = (uint32_t)h.vmax;
-    d.mcux = (W + 8 * d.hmax - 1) / (8 * d.hmax);
-    d.mcuy = (H + 8 * d.vmax - 1) / (8 * d.vmax);
-    uint32_t bpm = 0;
-    for (int c = 0; c < h.ncomp; c++) {
-      const JpegComponent &k = h.comp[c];
-      d.ch[c] = (uint32_t)k.h;
-      d.cv[c] = (uint32_t)k.v;
-      d.cdsw[c] = (uint32_t)(((uint64_t)W * k.h + d.hmax - 1) / d.hmax);
-      d.cdsh[c] = (uint32_t)(((uint64_t)H * k.v + d.vmax - 1) / d.vmax);
-      if (h.ncomp == 1) {
-        d.cbw[c] = (d.cdsw[c] + 7) / 8;
-        d.cbh[c] = (d.cdsh[c] + 7) / 8;
-        d.cfirst[c] = 0;
-        d.blk_comp[0] = 0;
-        bpm = 1;
-      } else {
-        d.cbw[c] = d.mcux * k.h;
-        d.cbh[c] = d.mcuy * k.v;
-        d.cfirst[c] = bpm;
-        for (int j = 0; j < k.h * k.v; j++) d.blk_comp[bpm + j] = (uint8_t)c;
-        bpm += (uint32_t)(k.h * k.v);
-      }
-    }
-    d.bpm = bpm;
-    d.comp_bits = 0;
-    for (uint32_t k = 0; k < bpm; k++) d.comp_bits |= (uint32_t)d.blk_comp[k] << (2 * k);
-    d.total_blocks = h.ncomp == 1 ? d.cbw[0] * d.cbh[0] : d.mcux * d.mcuy * bpm;
-    d.restart = (uint32_t)h.restart;
-    d.blocks_per_seg = d.restart * bpm;
-    // Huffman slots: unique pool indices per image
-    int nslots = 0;
-    auto slot_of = [&](int pidx) {
-      for (int s = 0; s < nslots; s++)
-        if (d.hslot[s] == pidx) return s;
-      d.hslot[nslots] = (uint16_t)pidx;
-      return nslots++;
-    };
-    d.slotmap = 0;
-    for (int c = 0; c < h.ncomp; c++) {
-      if (!h.progressive) {
-        d.slotmap |= (uint32_t)slot_of(pool_huff(h.dc[h.comp[c].td])) << ((2 * c) * 4);
-        d.slotmap |= (uint32_t)slot_of(pool_huff(h.ac[h.comp[c].ta])) << ((2 * c + 1) * 4);
-      }
-      d.qpool[c] = (uint16_t)pool_quant(h.q[h.comp[c].tq]);
-    }
-    d.nslots = (uint8_t)nslots;
-    b.max_slots = std::max<uint32_t>(b.max_slots, (uint32_t)nslots);
-    if (!h.progressive) {  // distinct AC slots (k_huff_sync builds a multi-symbol lookup for each, up to 3)
-      uint32_t acs = 0;
-      for (int c = 0; c < h.ncomp; c++) acs |= 1u << ((d.slotmap >> ((2 * c + 1) * 4)) & 15u);
-      b.max_ac = std::max<uint32_t>(b.max_ac, std::min<uint32_t>((uint32_t)__builtin_popcount(acs), kMultiLuts));
-    }
-    if (h.progressive) {  // scans decoded by k_prog_scan (records built once the source address is known)
-      d.prog = (uint32_t)h.scans.size();
-      if (host_io) in_off[i] = IN.take(lens[i] + 16, 16);
-    } else {
-    // entropy data
-    d.scan_len = (uint32_t)(h.scan_end - h.scan_off);
-    // Per-image subsequence size (option "sub_density" T > 0): a lane's
-    // decode time follows its symbols and blocks, not its bits, so images
-    // with few coded bits per block (flat, low quality: short EOB-heavy
-    // codes, ~2x the symbols per bit) take shorter ranges -- half below T
-    // bits per block, a quarter below T / 2 -- and their workgroups stop
-    // forming the entropy kernels' tail.
-    d.sub_bits = sub_bits;
-    if (sub_density_ > 0 && sub_bits_ == 0) {
-      const double bpb = (double)d.scan_len * 8.0 / (double)std::max<uint32_t>(1, d.total_blocks);
-      if (bpb < sub_density_ * 0.5 && sub_bits >= 2048)
-        d.sub_bits = sub_bits / 4;
-      else if (bpb < sub_density_ && sub_bits >= 1024)
-        d.sub_bits = sub_bits / 2;
-    }
-    // completed blocks go straight to plane pixels inside k_huff_write (not
-    // with decode-once staging, whose k_huff_scatter writes coefficients)
-    d.idct_fused = (idct_fused_ && !entropy_once_) ? 1u : 0u;
-    // k_huff_write splits each range at the sync pass's half-way checkpoint
-    // (option "write_split"): needs that checkpoint, no restart markers and
-    // the plain write path
-    if (write_split_ && d.ckpt && !d.idct_fused && !entropy_once_ && h.restart == 0 && d.sub_bits >= 1024 &&
-        d.sub_bits / 2 / kCkptBits - 1 < num_ckpt(d.sub_bits))
-      d.ckpt |= 2u;
-    if (d.idct_fused) b.any_fused = true;
-    // lead-in before each subsequence (lead_in in dg_entropy.h): covers the
-    // self-synchronisation distance, which is longest for 6-block MCUs
-    // (4:2:0; p99.9 ~7 kbit on the bench corpus, tools/sync_stats.cpp).
-    // Option "lead_big" (4096): shorter than that tail, but a wrong entry
-    // guess only costs a re-decode up to the first checkpoint where it merges
-    // (6144 -> 4096: +1.3% on configs[1]; 2048 / 1024 slower on configs[2])
-    d.lead_bits = lead_bits_ >= 0 ? (uint32_t)lead_bits_ : small ? lead_small_ : (bpm >= 4 ? lead_big_ : 2048u);
-    // shorter ranges of symbol-dense images get a proportionally shorter lead-in (option
-    // "lead_density"): their codes are short, so the decoder self-synchronises in fewer bits
-    if (lead_density_ && lead_bits_ < 0 && d.sub_bits < sub_bits)
-      d.lead_bits = std::max<uint32_t>(1024u, d.lead_bits / (sub_bits / d.sub_bits));
-    d.nsub = std::max<uint32_t>(1, (uint32_t)(((uint64_t)d.scan_len * 8 + d.sub_bits - 1) / d.sub_bits));
-    d.sub_base = sub_base;
-    sub_base += d.nsub;
-    d.ckpt_base = (uint32_t)ckpt_total;
-    ckpt_total += (uint64_t)d.nsub * num_ckpt(d.sub_bits);
-    d.nchunk = std::max<uint32_t>(1, (d.scan_len + kDestuffChunk - 1) / kDestuffChunk);
-    uint32_t mcus = h.ncomp == 1 ? d.total_blocks : d.mcux * d.mcuy;
-    d.mk_cap = (d.restart ? mcus / d.restart + 2 : 0) + 64;
-    d.ds_lsw = 0;
-    while ((32u << d.ds_lsw) < d.sub_bits) d.ds_lsw++;
-    o.ds = L.take((size_t)ds_words_alloc(d.nsub, d.ds_lsw) * 4, 256);
-    if (entropy_once_ && d.sub_bits <= 8192) {  // decode-once staging (dg_entropy.h StageCtx)
-      d.stage_cap = (d.sub_bits / 2 + d.sub_bits / 8 + 64 + 3) / 4;
-      o.stage = L.take((size_t)((d.nsub + 63) / 64) * d.stage_cap * 64 * 16, 256);
-      b.stage_on = true;
-    }
-    o.mk = L.take((size_t)d.mk_cap * 4, 16);
-    o.chunk = L.take((size_t)d.nchunk * 16, 16);
-    if (host_io) in_off[i] = IN.take(lens[i] + 16, 16);
-    }  // sequential
-    // buffers
-    o.coef = CO.take((size_t)d.total_blocks * 128);
-    // sparse blocks: k_huff_write's cooperative flush + k_idct_t only (not the
-    // fused / decode-once writers, k_idct or k_band_dec; progressive scans
-    // write whole blocks)
-    o.ccnt = (sparse_coef_ && idct_thread_ && !d.prog && !d.idct_fused && !entropy_once_)
-                 ? CO.take((size_t)d.total_blocks, 64) + 1
-                 : 0;
-    for (int c = 0; c < 3; c++) o.plane[c] = (size_t)-1;  // allocated after the pass plan (not for k_band_dec)
-    C = d.dec_c;
-    colour = h.ncomp == 3;
-    if (h.ncomp == 3) {
-      d.pix_stride = (uint32_t)align_up((size_t)W * 3, 16);
-      cur_stride = d.pix_stride;  // the RGB image is only materialised if no pass fuses it
-    } else {
-      cur_stride = (size_t)d.cbw[0] * 8;
-    }
-    }  // JPEG
-    // resize plan (image_processing.rs:264-325)
-    d.out_w = p.out_w;
-    d.out_h = p.out_h;
-    d.out_c = p.out_c;
-    d.out_stride = p.out_w * p.out_c * (p.bit_depth == 16 ? 2 : 1);
-    // Passes (fast_image_resize semantics, B1): call 1 resizes W x H to the
-    // scaled nw x nh, call 2 crops the bucket out of it with a possibly
-    // fractional (x.5) offset.  An integral crop offset on an axis is only a
-    // window of call 1's outputs on that axis, so call 1's pass computes just
-    // that window (out0 / width) and call 2 needs no pass there; a fractional
-    // offset keeps call 2's sub-pixel pass.  Without a call-1 pass on an axis
-    // the window is a plain offset into the current image.
-    uint32_t cw = W, chh = H;     // extent of the current image's valid window
-    uint32_t xoff = 0, yoff = 0;  // window origin (pixels, rows) inside the current buffer
-    int last_stage = -1;
-    auto add_pass = [&](int stage, uint32_t kind, double in0, double in1, uint32_t in_size, uint32_t out_size,
-                        uint32_t out0, uint32_t width, uint32_t rows, uint32_t row0) -> ResizePass & {
-      ResizePass &ps = d.pass[stage];
-      ps.kind = kind;
-      ps.in0 = in0;
-      ps.in1 = in1;
-      ps.in_size = in_size;
-      ps.out_size = out_size;
-      ps.out0 = out0;
-      ps.ksize = fir_ksize(in0, in1, out_size);
-      ps.src_stride = (uint32_t)cur_stride;
-      ps.width = width;
-      ps.rows = rows;
-      ps.row0 = row0;
-      ps.bands = hb_bands_;
-      ps.C = C;
-      ps.dst_stride = (uint32_t)align_up((size_t)width * C, 16);
-      o.pass_srcoff[stage] = (size_t)xoff * C;  // column window of the source (V passes)
-      o.pass_dst[stage] = (alias ? LT : L).take((size_t)ps.dst_stride * ps.rows);
-      o.late |= alias ? 8u << stage : 0u;
-      o.pass_cache[stage] = ccache_lookup(ps, b, o.pass_hit[stage]);
-      if (o.pass_cache[stage] < 0) {
-        o.pass_coef[stage] = L.take((size_t)out_size * ps.ksize * 2);
-        o.pass_bounds[stage] = L.take((size_t)out_size * 8);
-      }
-      cur_stride = ps.dst_stride;
-      last_stage = stage;
-      return ps;
-    };
-    if (has_cfg_ && !(W == p.out_w && H == p.out_h)) {
-      uint32_t nw, nh;
-      scaled_size(W, H, p.out_w, p.out_h, nw, nh);
-      double l, t, bw, bh;
-      fit_crop_box(nw, nh, p.out_w, p.out_h, l, t, bw, bh);
-      // A window is exact for a scale-1 crop at an integral offset.  The crop box
-      // comes out of f64 arithmetic (640x480 -> top 6.000000000000028, height
-      // 431.99999999999994): deviations this small leave the i16 Lanczos
-      // weights exactly one-hot (they are < 2^-15 off), so the sub-pixel pass
-      // would copy pixel rint(offset) + i and the window is still bit-exact.
-      auto near_int = [](double v, double tgt) { return std::fabs(v - tgt) <= 1e-6; };
-      const bool fold_x = near_int(l, std::rint(l)) && near_int(bw, (double)p.out_w);
-      const bool fold_y = near_int(t, std::rint(t)) && near_int(bh, (double)p.out_h);
-      const uint32_t lx = fold_x ? (uint32_t)std::rint(l) : 0u, ty = fold_y ? (uint32_t)std::rint(t) : 0u;
-      if (nw != W) {  // call 1, horizontal
-        ResizePass &ps = add_pass(0, 1, 0.0, (double)W, W, nw, fold_x ? lx : 0u, fold_x ? p.out_w : nw, chh, 0);
-        ps.mode = h_pass_mode(ps, colour);
-        cw = ps.width;
-      } else if (fold_x) {
-        xoff = lx;
-        cw = p.out_w;
-      }
-      if (nh != H) {  // call 1, vertical (reads the column window, absorbs xoff)
-        ResizePass &ps = add_pass(1, 2, 0.0, (double)H, H, nh, fold_y ? ty : 0u, cw, fold_y ? p.out_h : nh, 0);
-        chh = ps.rows;
-        xoff = 0;
-      } else if (fold_y) {
-        yoff = ty;
-        chh = p.out_h;
-      }
-      if (!fold_x) {  // call 2, horizontal sub-pixel crop (reads the row window, absorbs yoff)
-        ResizePass &ps = add_pass(2, 1, l, l + bw, cw, p.out_w, 0, p.out_w, chh, yoff);
-        ps.mode = h_pass_mode(ps, false);
-        cw = p.out_w;
-        yoff = 0;
-      }
-      if (!fold_y) {  // call 2, vertical sub-pixel crop (reads the column window, absorbs xoff)
-        add_pass(3, 2, t, t + bh, chh, p.out_h, 0, cw, p.out_h, 0);
-        chh = p.out_h;
-        xoff = 0;
-      }
-      // U8x2 / U8x4: fast_image_resize multiplies colour by alpha before each
-      // convolution call and divides after (mul_div_alpha); a call
-      // whose crop box has the destination's size at integral offsets is a
-      // copy and touches no alpha.  Programs run in place at three points.
-      if (C == 2 || C == 4) {
-        const bool call1 = !(nw == W && nh == H);
-        const bool call2 = !(bw == (double)p.out_w && bh == (double)p.out_h && l == std::floor(l) &&
-                             t == std::floor(t));
-        const bool call2_passes = d.pass[2].kind || d.pass[3].kind;
-        const int s1 = d.pass[1].kind ? 1 : 0;  // last call-1 pass (when call1)
-        auto set = [&](int k, int stage, uint32_t w, uint32_t rows, uint32_t prog) {
-          if (!prog) return;
-          o.aop_stage[k] = stage;
-          d.aop[k].width = w;
-          d.aop[k].rows = rows;
-          d.aop[k].prog = prog;
-          b.any_alpha = true;
-        };
-        set(0, -1, W, H, call1 ? 1u : 0u);
-        uint32_t prog1 = 0, sh = 0;
-        auto push = [&](uint32_t op) {
-          prog1 |= op << sh;
-          sh += 2;
-        };
-        if (call1) push(2);
-        if (call2) push(1);
-        if (call2 && !call2_passes) push(2);
-        if (call1)
-          set(1, s1, d.pass[s1].width, d.pass[s1].rows, prog1);
-        else
-          set(1, -1, W, H, prog1);
-        if (call2 && call2_passes) set(2, d.pass[3].kind ? 3 : 2, p.out_w, p.out_h, 2u);
-      }
-    }
-    // colour images whose first pass is not a fused H pass need the RGB image
-    d.color_fused = colour && d.pass[0].kind == 1 && (d.pass[0].mode & kHFused);
-    if (hv_fused_ && hv_fusable(d.pass[0], d.pass[1])) d.pass[0].mode |= kHVFused;
-    if (p.fmt == kFmtJpeg) {
-      // k_band_dec decodes pass[0]'s source from the coefficients: no planes
-      const uint32_t dm = band_dec_ ? band_dec_mode(d, d.pass[0]) : 0u;
-      d.pass[0].mode |= dm;
-      if (dm) stat_band_dec_++;
-      if (!dm)
-        for (uint32_t c = 0; c < d.ncomp; c++) {
-          // half-rate chroma as 8-byte records (dg_plane.h, option "chroma_rec"): twice the bytes
-          const bool rec = chroma_rec_ && d.ncomp == 3 && d.hmax == 2 * d.ch[c];
-          if (rec) d.crec |= 1u << c;
-          o.plane[c] = L.take((size_t)d.cbw[c] * 8 * d.cbh[c] * 8 * (rec ? 2 : 1));
-        }
-    }
-    if (colour && !d.color_fused) o.pix = L.take((size_t)d.pix_stride * H);
-    // final write: the last pass writes straight into the output when the
-    // channel count is unchanged; otherwise (or with no pass) k_copy runs.
-    if (last_stage >= 0 && d.out_c == C) {
-      d.pass[last_stage].dst_stride = d.out_stride;
-      o.pass_dst[last_stage] = (size_t)-1;  // -> out
-      d.copy_needed = 0;
-    } else {
-      d.copy_needed = 1;
-      d.final_src_c = C;
-      d.final_src_stride = (uint32_t)cur_stride;
-      o.final_off = (size_t)yoff * cur_stride + (size_t)xoff * C;  // an uncomputed integral crop
-      if (d.sample_bytes == 2)  // 16-bit PNG (never resized: plan_image): u16 copy, or to_rgb8
-        d.copy_mode = p.bit_depth == 16 ? 5 : 6;
-      else if (d.out_c == C)
-        d.copy_mode = 0;
-      else if (C == 1)
-        d.copy_mode = 1;  // L8 -> RGB8
-      else if (C == 4)
-        d.copy_mode = 2;  // RGBA8 -> RGB8 over gray
-      else  // LA8 -> RGB8: resized images went through image_to_dyn_image's GrayImage (B3)
-        d.copy_mode = (has_cfg_ && !(W == p.out_w && H == p.out_h)) ? 3 : 4;
-    }
-    if (host_io) {
-      o.out = (alias ? LT : L).take(p.out_bytes, 16);
-      o.late |= alias ? 4u : 0u;
-      b.out_dev_off[i] = o.out;
-      out_total += p.out_bytes;
-    }
-    if (p.encode && p.enc_png) {  // PNG re-encode (dg_penc.hip): the transform lands in tout
-      EncDesc &e = d.enc;
-      e.active = 1;
-      e.png = 1;
-      e.w = p.out_w;
-      e.h = p.out_h;
-      e.C = p.enc_la_gray ? 1 : p.out_c;
-      e.src_stride = p.enc_la_gray ? p.out_w : d.out_stride;
-      const uint64_t nf = (uint64_t)e.h * ((uint64_t)e.w * e.C + 1);
-      e.nblocks = (uint32_t)((nf + 1023) / 1024);
-      const std::vector<uint8_t> hdr = png_enc_header(e.w, e.h, e.C);
-      e.hdr_len = (uint32_t)hdr.size();
-      o.hdr = b.blob.size();
-      b.blob.insert(b.blob.end(), hdr.begin(), hdr.end());
-      o.tout = L.take(p.img_bytes + 16, 256);
-      o.ecoef = L.take((size_t)nf + 16, 256);
-      o.ebits = L.take((size_t)e.nblocks * 4, 256);
-      o.eaux = L.take((size_t)e.nblocks * 8, 256);
-      o.ewords = (size_t)((3 + 9 * nf + 7 + 64) / 8 + 64) / 4 * 4;  // size for now; placed after the loop
-      b.any_enc = true;
-    } else if (p.encode) {  // the transform lands in tout; the JPEG goes to the caller's buffer
-      EncDesc &e = d.enc;
-      e.active = 1;
-      e.w = p.out_w;
-      e.h = p.out_h;
-      e.C = p.out_c;
-      e.ncomp = p.out_c <= 2 ? 1 : 3;
-      e.mode = p.enc_la_gray ? 1 : 0;
-      e.src_stride = d.out_stride;
-      e.nbx = (p.out_w + 7) / 8;
-      e.nby = (p.out_h + 7) / 8;
-      e.nblocks = e.nbx * e.nby * e.ncomp;
-      int qual = cfg_.jpeg_quality;
-      uint8_t q[2][64];
-      jpeg_enc_qtables(qual, q);
-      memcpy(e.q, q, sizeof(q));
-      const std::vector<uint8_t> hdr = jpeg_enc_header(p.out_w, p.out_h, (int)e.ncomp, qual);
-      e.hdr_len = (uint32_t)hdr.size();
-      o.hdr = b.blob.size();
-      b.blob.insert(b.blob.end(), hdr.begin(), hdr.end());
-      o.tout = L.take(p.img_bytes + 16, 256);
-      o.ecoef = L.take((size_t)e.nblocks * 128, 256);
-      o.ebits = L.take((size_t)e.nblocks * 4, 256);
-      o.ewords = (size_t)(e.nblocks * 210ull + 64) / 4 * 4 + 16;  // size for now; placed after the loop
-      b.any_enc = true;
-    }
-    b.desc_of[i] = (int)b.descs.size();
-    b.descs.push_back(d);
-    offs.push_back(o);
-    (void)last_stage;
-  }
-  if (alias) {  // the late buffers and the chunk entries share one region after the early ones
-    const size_t r0 = align_up(L.off, 256);
-    L.off = r0 + std::max(LT.off, CH.off);
-    for (Offs &o : offs) {
-      if (o.late & 1u) o.unf += r0;
-      if (o.late & 2u) o.pix += r0;
-      if (o.late & 4u) {
-        o.out += r0;
-        b.out_dev_off[o.img] = o.out;
-      }
-      for (int s = 0; s < kStages; s++)
-        if ((o.late & (8u << s)) && o.pass_dst[s] != (size_t)-1) o.pass_dst[s] += r0;
-    }
-    for (InfChunk &c : b.ichunks) {
-      c.out += r0;
-      c.tab += r0;
-    }
-  }
-  b.total_subs = sub_base;
-  if (b.any_enc) {  // encoder bit buffers: one contiguous region, zeroed with one memset per batch
-    size_t tot = 0;
-    for (Offs &o : offs)
-      if (o.ewords) {
-        const size_t sz = o.ewords;
-        o.ewords = tot;
-        tot += (sz + 255) / 256 * 256;
-      }
-    b.words_off = L.take(tot, 256);
-    b.words_bytes = tot;
-    for (Offs &o : offs)
-      if (o.tout) o.ewords += b.words_off;
-    EncTables et;
-    jpeg_enc_tables(et);
-    while (b.blob.size() % 16) b.blob.push_back(0);
-    b.enctab_off = b.blob.size();
-    b.blob.insert(b.blob.end(), (const uint8_t *)&et, (const uint8_t *)&et + sizeof(et));
-  }
-  // PNG unfilter: one progress flag per 64-row band of every plane
-  b.uf_n = 0;
-  b.uf_maxbpp = 1;
-  for (ImageDesc &dd : b.descs)
-    if (dd.fmt == kFmtPng) {
-      dd.png.uf_flag0 = b.uf_n;
-      b.uf_n += png_bands(dd);
-      b.uf_maxbpp = std::max(b.uf_maxbpp, dd.png.bpp);
-    }
-  b.uf_flags_off = b.uf_n ? L.take((size_t)(b.uf_n + 1) * 4) : 0;
-  b.pf_n = 0;
-  for (const ImageDesc &dd : b.descs)
-    if (dd.fmt == kFmtJpeg) b.pf_n += dd.prog;
-  b.pf_off = b.pf_n ? L.take((size_t)(b.pf_n + 2) * 4) : 0;  // AC ticket, progress words, DC ticket
-  // k_destuff_one: a ticket word + one state word per destuff chunk (zeroed per batch)
-  b.ds_n = 0;
-  for (const ImageDesc &dd : b.descs)
-    if (dd.fmt == kFmtJpeg && !dd.prog) b.ds_n += dd.nchunk;
-  b.ds_state_off = (destuff_one_ && b.ds_n) ? L.take((size_t)(b.ds_n + 1) * 8) : 0;
-  const size_t subs_off = L.take(b.total_subs * sizeof(SubState));
-  const size_t ckpt_off = L.take(std::max<uint64_t>(1, ckpt_total) * sizeof(Ckpt));
-  // fused IDCT leftovers: at most one carried-in block per subsequence, plus
-  // the blocks of flushes with < 8 active lanes -- the tail of a wave, or
-  // every block of an image with fewer subsequences than that.  Sized for
-  // the worst case (all blocks of the fused images; 8 B each is small next
-  // to their 128 B of coefficients); k_idct_list clamps to it and finish()
-  // checks it.
-  uint64_t fused_blocks = 0;
-  for (const ImageDesc &dd : b.descs)
-    if (dd.idct_fused) fused_blocks += dd.total_blocks;
-  b.idct_cap = b.any_fused ? (uint32_t)std::min<uint64_t>(2 * b.total_subs + fused_blocks + 4096, 0xFFFFFFF0u) : 0u;
-  const size_t idct_list_off = L.take((size_t)b.idct_cap * 8 + 16);
-  // Device memory: under the budget (option "max_device_mb") a batch that
-  // does not fit even with the other slots drained goes back to the caller
-  // to be split (submit_split); without one, a failed allocation first
-  // finishes the other slots' batches and frees their buffers, then splits.
-  const size_t rs = L.off + 256, rc = CO.off + 256, ri = host_io ? IN.off + 64 : 0;
-  const bool planned = max_dev_bytes_ && budget_plan_ && &sl - slots_ < kMaxInflight;
-  if (planned) {
-    st = budget_planned_fit(sl, rs, rc, ri);
-    if (st) return st;
-  } else {
-    if (sl.views) free_slot_buffers(sl);  // (the budget plan was switched off)
-    if (!budget_fit(sl, rs, rc, ri)) return kNeedSplit;
-  }
-  for (int attempt = 0; !planned; attempt++) {
-    st = ensure(sl.scratch, rs, sl.st);
-    if (!st) st = ensure(sl.coef, rc, sl.st);
-    if (!st && host_io) st = ensure(sl.input, ri, sl.st);
-    if (st != DG_ERR_OOM) break;
-    if (attempt > 0) return kNeedSplit;
-    for (Slot &o : slots_) {
-      if (&o == &sl) continue;
-      if (o.batch && !o.batch->done && finish(o)) continue;
-      free_slot_buffers(o);
-    }
-    // the Lanczos table arena counts too (256 MiB by default): with every
-    // other batch finished only this one could read it
-    bool cache_busy = b.uses_ccache;
-    for (const Slot &o : slots_)
-      if (&o != &sl && o.batch && !o.batch->done && o.batch->uses_ccache) cache_busy = true;
-    if (!cache_busy && d_ccache_.p) {
-      ccache_index_clear();
-      ccache_.clear();
-      ccache_off_ = 0;
-      ccache_full_ = false;
-      hipFree(d_ccache_.p);
-      d_ccache_.p = nullptr;
-      d_ccache_.cap = 0;
-    }
-  }
-  if (st) return st;
-  sl.coef_bytes = CO.off;
-  // ---- 4. patch device addresses
-  char *S = (char *)sl.scratch.p;
-  for (InfChunk &c : b.ichunks) {
-    c.out = (uint64_t)(uintptr_t)(S + c.out);
-    c.tab = (uint64_t)(uintptr_t)(S + c.tab);
-  }
-  int k = 0;
-  for (int i = 0; i < n; i++) {
-    if (b.desc_of[i] < 0) continue;
-    ImageDesc &d = b.descs[b.desc_of[i]];
-    const Offs &o = offs[k++];
-    const JpegHeader &h = b.plans[i].hdr;
-    const uint8_t *src = host_io ? (const uint8_t *)sl.input.p + in_off[i] : d_srcs[i];
-    const uint64_t user_out = host_io ? (uint64_t)(uintptr_t)(S + o.out) : (uint64_t)(uintptr_t)outs[i];
-    const uint64_t out = d.enc.active ? (uint64_t)(uintptr_t)(S + o.tout) : user_out;
-    d.out = out;
-    if (d.enc.active) {
-      EncDesc &e = d.enc;
-      e.src = out;
-      e.out = user_out;
-      e.coef = (uint64_t)(uintptr_t)(S + o.ecoef);
-      e.bits = (uint64_t)(uintptr_t)(S + o.ebits);
-      e.words = (uint64_t)(uintptr_t)(S + o.ewords);
-      e.aux = o.eaux ? (uint64_t)(uintptr_t)(S + o.eaux) : 0;
-      e.hdr = o.hdr + 1;  // blob offset + 1: made absolute with the meta buffer
-    }
-    if (d.fmt == kFmtPng) {
-      const PngHeader &g = b.plans[i].png;
-      PngDesc &pd = d.png;
-      pd.zs = (uint64_t)(uintptr_t)(S + o.zs);
-      pd.raw = (uint64_t)(uintptr_t)(S + o.raw);
-      pd.unf = (uint64_t)(uintptr_t)(S + o.unf);
-      d.pix = pd.expand ? (uint64_t)(uintptr_t)(S + o.pix) : pd.unf;
-      pd.pal = g.ctype == 3 ? o.pal + 1 : 0;  // blob offset + 1, made absolute with the meta buffer
-      uint64_t zo = 0;
-      for (size_t c = 0; c < g.idat_off.size(); c++) {
-        GatherJob j;
-        j.src = (uint64_t)(uintptr_t)(src + g.idat_off[c]);
-        j.dst = pd.zs + zo;
-        j.len = g.idat_len[c];
-        j.pad = 0;
-        zo += g.idat_len[c];
-        b.gjobs.push_back(j);
-      }
-    } else {
-    d.scan = (uint64_t)(uintptr_t)(src + h.scan_off);
-    d.coef = (uint64_t)(uintptr_t)((char *)sl.coef.p + o.coef);
-    d.ccnt = (o.ccnt && !(d.pass[0].mode & kHDecode)) ? (uint64_t)(uintptr_t)((char *)sl.coef.p + o.ccnt - 1) : 0;
-    if (d.prog) {
-      // one record per scan; level = 1 + the highest level of an earlier scan
-      // sharing a component and an overlapping coefficient band
-      const size_t first = b.pscans.size();
-      for (size_t j = 0; j < h.scans.size(); j++) {
-        const JpegScan &sc = h.scans[j];
-        ProgScan r;
-        memset(&r, 0, sizeof(r));
-        r.data = (uint64_t)(uintptr_t)(src + sc.off);
-        r.len = (uint32_t)(sc.end - sc.off);
-        r.image = (uint32_t)b.desc_of[i];
-        r.ns = (uint32_t)sc.ns;
-        for (int q = 0; q < sc.ns; q++) {
-          r.comp[q] = (uint32_t)sc.comp[q];
-          r.dc[q] = sc.dc_tab[q] >= 0 ? (uint16_t)pool_huff(h.tables[sc.dc_tab[q]]) : 0;
-        }
-        r.ac = sc.ac_tab >= 0 ? (uint16_t)pool_huff(h.tables[sc.ac_tab]) : 0;
-        r.ss = (uint32_t)sc.ss;
-        r.se = (uint32_t)sc.se;
-        r.ah = (uint32_t)sc.ah;
-        r.al = (uint32_t)sc.al;
-        r.restart = (uint32_t)sc.restart;
-        r.first = (uint32_t)first;
-        r.next = kProgNoScan;
-        r.pflags = 0;
-        uint32_t lvl = 0;
-        for (size_t e = 0; e < j; e++) {
-          const JpegScan &pr = h.scans[e];
-          if (pr.se < sc.ss || sc.se < pr.ss) continue;
-          bool share = false;
-          for (int x = 0; x < pr.ns; x++)
-            for (int y = 0; y < sc.ns; y++) share |= pr.comp[x] == sc.comp[y];
-          if (share) {
-            lvl = std::max(lvl, b.pscans[first + e].level + 1);
-            if (h.scans.size() <= kProgMaxDepScans) r.deps |= 1ull << e;  // larger files: chained only
-          }
-        }
-        r.level = lvl;
-        b.pscans.push_back(r);
-      }
-    } else {
-    d.ds = (uint64_t)(uintptr_t)(S + o.ds);
-    d.stage = d.stage_cap ? (uint64_t)(uintptr_t)(S + o.stage) : 0;
-    d.mk = (uint64_t)(uintptr_t)(S + o.mk);
-    d.chunk = (uint64_t)(uintptr_t)(S + o.chunk);
-    }
-    for (int c = 0; c < h.ncomp; c++) d.plane[c] = o.plane[c] == (size_t)-1 ? 0 : (uint64_t)(uintptr_t)(S + o.plane[c]);
-    d.pix = h.ncomp == 3 && !d.color_fused ? (uint64_t)(uintptr_t)(S + o.pix) : 0;
-    }  // JPEG
-    uint64_t cur = (d.fmt == kFmtPng || h.ncomp == 3) ? d.pix : d.plane[0];
-    const uint64_t decoded = cur;
-    const uint32_t decoded_stride = d.fmt == kFmtPng ? d.pix_stride : (h.ncomp == 3 ? d.pix_stride : d.cbw[0] * 8);
-    for (int s = 0; s < kStages; s++) {
-      ResizePass &ps = d.pass[s];
-      if (!ps.kind) continue;
-      ps.src = cur + o.pass_srcoff[s];
-      ps.dst = o.pass_dst[s] == (size_t)-1 ? out : (uint64_t)(uintptr_t)(S + o.pass_dst[s]);
-      if (o.pass_cache[s] >= 0) {  // cached tables: bounds, then the weights
-        const CEntry &e = ccache_[o.pass_cache[s]];
-        char *cb = (char *)d_ccache_.p + e.off;
-        ps.bounds = (uint64_t)(uintptr_t)cb;
-        ps.coef = (uint64_t)(uintptr_t)(cb + (size_t)ps.out_size * 8);
-        if (o.pass_hit[s]) {
-          ps.precision = e.precision;
-          b.coef_hit.resize(b.descs.size(), 0);
-          b.coef_hit[b.desc_of[i]] |= (uint8_t)(1u << s);
-        } else
-          b.ccache_prod.push_back({b.desc_of[i], s, o.pass_cache[s]});
-      } else {
-        ps.coef = (uint64_t)(uintptr_t)(S + o.pass_coef[s]);
-        ps.bounds = (uint64_t)(uintptr_t)(S + o.pass_bounds[s]);
-      }
-      cur = ps.dst;
-    }
-    d.final_src = cur + (d.copy_needed ? o.final_off : 0);
-    for (uint32_t k = 0; k < kAlphaPoints; k++) {
-      if (!d.aop[k].prog) continue;
-      const int sg = o.aop_stage[k];
-      if (sg < 0) {
-        d.aop[k].buf = decoded;
-        d.aop[k].stride = decoded_stride;
-        d.aop[k].on_decoded = 1;
-      } else {
-        d.aop[k].buf = d.pass[sg].dst;
-        d.aop[k].stride = d.pass[sg].dst_stride;
-      }
-    }
-    (void)subs_off;
-  }
-  phase(2);
-  // ---- 5. workgroup lists
-  for (int l = 0; l < L_COUNT; l++) {  // sized from the previous batch: no regrowth copies
-    b.lists[l].clear();
-    b.lists[l].reserve(list_hint_[l] + list_hint_[l] / 4);
-  }
-  std::vector<WgItem> hb[2][2][4];  // band H items per (stage, fused fill, weight-count class)
-  std::vector<WgItem> hvl[2];       // k_resize_hv items per H weight class
-  std::vector<WgItem> decl[2];      // k_band_dec items per segment class
-  std::vector<WgItem> hm[2][2][2];  // k_resize_hm items per (stage, fused fill, K steps)
-  for (int di = 0; di < (int)b.descs.size(); di++) {
-    const ImageDesc &d = b.descs[di];
-    const uint32_t I = (uint32_t)di;
-    for (uint32_t k = 0; k < kAlphaPoints; k++)
-      if (d.aop[k].prog) {
-        const uint32_t cnt = d.aop[k].width * d.aop[k].rows;
-        for (uint32_t it = 0; it < cnt; it += 256) b.lists[L_ALPHA0 + k].push_back({I, it});
-      }
-    if (d.fmt == kFmtPng) {
-      b.lists[L_PNG].push_back({I, 0});
-      if (d.png.nchunks) {
-        b.lists[L_INF_RES].push_back({I, 0});
-        for (uint32_t k = 1; k < d.png.nchunks; k++) b.lists[L_INF_FIND].push_back({d.png.chunk0 + k, 0});
-      }
-      if (d.sample_bytes == 2)
-        for (uint32_t it = 0; it < (d.width + 1) / 2 * d.height; it += 256) b.lists[L_EXPAND16].push_back({I, it});
-      else if (d.png.expand)
-        for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_EXPAND].push_back({I, it});
-    } else {
-    if (d.prog) {
-      const uint64_t bytes = (uint64_t)d.total_blocks * 128;
-      for (uint32_t c = 0; (uint64_t)c * kProgZeroBytes < bytes; c++) b.lists[L_PROG_ZERO].push_back({I, c});
-    } else {
-    // split ranges (write_split): 128 ranges per k_huff_write workgroup, two lanes each
-    const uint32_t wstep = (d.ckpt & 2u) ? kSubPerWg / 2 : kSubPerWg;
-    for (uint32_t w = 0; w < d.nsub; w += wstep) b.lists[L_HUFF].push_back({I, w});
-    for (uint32_t w = 0; w < d.nsub; w += kSubPerWg - 1) b.lists[L_SYNC].push_back({I, w});
-    b.descs[di].ds_state0 = (uint32_t)b.lists[L_DESTUFF].size();  // k_destuff_one's state words, list order
-    for (uint32_t c = 0; c < d.nchunk; c++) b.lists[L_DESTUFF].push_back({I, c});
-    b.lists[L_SCAN].push_back({I, 0});
-    }
-    uint32_t items = 0;
-    for (uint32_t c = 0; c < d.ncomp; c++) items += d.cbh[c] * ((d.cbw[c] + 63) / 64);  // kIdctBlocks
-    if (!d.idct_fused && !(d.pass[0].mode & kHDecode))  // fused: k_huff_write (+ k_idct_list) / k_band_dec
-      for (uint32_t it = 0; it < items; it += idct_thread_ ? kIdctItemStride : 1u) b.lists[L_IDCT].push_back({I, it});
-    if (d.ncomp == 3 && !d.color_fused) {
-      uint32_t q = (d.width + 7) / 8 * d.height;
-      for (uint32_t it = 0; it < q; it += 256) b.lists[L_COLOR].push_back({I, it});
-    }
-    }  // JPEG
-    const bool hv = (d.pass[0].mode & kHVFused) != 0;
-    if (hv) {  // one workgroup per (V segment of kHVRows rows, column tile)
-      const uint32_t tiles = (d.pass[0].width + kHBandCols - 1) / kHBandCols;
-      const uint32_t cnt = tiles * ((d.pass[1].rows + kHVRows - 1) / kHVRows);
-      const int cls = d.pass[0].ksize + 1 <= 8 ? 0 : 1;
-      for (uint32_t it = 0; it < cnt; it++) hvl[cls].push_back({I, it});
-    }
-    if (d.pass[0].mode & kHDecode) {  // one workgroup per (group of dec_strips 16-row strips, 128-column tile)
-      const ResizePass &ps = d.pass[0];
-      const uint32_t tiles = (ps.width + kDecCols - 1) / kDecCols;
-      const uint32_t strips = (ps.row0 + ps.rows + 15) / 16 - ps.row0 / 16;
-      const uint32_t cnt = tiles * ((strips + dec_strips_ - 1) / dec_strips_);
-      for (uint32_t it = 0; it < cnt; it++) decl[(ps.mode & kHDecWide) ? 1 : 0].push_back({I, it});
-    }
-    for (int s = 0; s < kStages; s++) {
-      const ResizePass &ps = d.pass[s];
-      if (!ps.kind) continue;
-      if (!(di < (int)b.coef_hit.size() && (b.coef_hit[di] >> s) & 1u)) b.lists[L_COEF].push_back({I, (uint32_t)s});
-      if (hv && s < 2) continue;  // k_resize_hv runs both
-      if (s == 0 && (ps.mode & kHDecode)) continue;  // k_band_dec runs it
-      if (ps.kind == 1 && (ps.mode & kHDirect)) {  // one workgroup per (row, 512-column tile)
-        uint32_t cnt = ps.rows * ((ps.width + 511) / 512);
-        for (uint32_t it = 0; it < cnt; it++) b.lists[s == 0 ? L_RHX0 : L_RHX2].push_back({I, it});
-      } else if (ps.kind == 1) {  // one workgroup per (band of rows, column tile)
-        const uint32_t rows_per_wg = kHBandRows * ps.bands;
-        uint32_t cnt = ((ps.rows + rows_per_wg - 1) / rows_per_wg) * ((ps.width + kHBandCols - 1) / kHBandCols);
-        // k_resize_hb<K> reads taps in even-aligned pairs: a window starting
-        // at an odd segment position spans ksize + 1 positions
-        const uint32_t kk = ps.ksize + 1;
-        int cls = kk <= 8 ? 0 : kk <= 16 ? 1 : kk <= 32 ? 2 : 3;
-        // the 8- and 16-tap kernels stage narrower segments (hseg_px in kernels.hip)
-        while (cls < 2 && h_pass_span(ps) > (cls == 0 ? 192.0 : 384.0)) cls++;
-        const int fused = (ps.mode & kHFused) ? 1 : 0;
-        const uint32_t ks = h_mfma_ ? h_mfma_steps(ps) : 0u;
-        if (ks)
-          for (uint32_t it = 0; it < cnt; it++) hm[s / 2][fused][ks - 1].push_back({I, it});
-        else
-          for (uint32_t it = 0; it < cnt; it++) hb[s / 2][fused][cls].push_back({I, it});
-        if (fused && d.sem) b.h_zune = 1;  // the planar fused kernels of the zune fill classes
-      } else if (v_tile_ && (ps.src_stride & 15) == 0) {  // k_resize_vt: 4 waves of (R rows x 1 KiB) tiles
-        const uint32_t units = (ps.width * ps.C + 15) / 16;
-        const uint32_t tiles = (units + 63) / 64 * ((ps.rows + v_tile_ - 1) / v_tile_);
-        for (uint32_t it = 0; it < tiles; it += 4) b.lists[s == 1 ? L_RVT1 : L_RVT3].push_back({I, it});
-        b.v_tile = v_tile_;
-      } else {
-        uint32_t cnt = (ps.width * ps.C + 15) / 16 * ps.rows;
-        for (uint32_t it = 0; it < cnt; it += 256 * v_units_) b.lists[L_RH0 + s].push_back({I, it});
-      }
-    }
-    if (d.copy_needed) {
-      uint32_t cnt = d.out_w * d.out_h;
-      for (uint32_t it = 0; it < cnt; it += 256) b.lists[L_COPY].push_back({I, it});
-    }
-    if (d.enc.active && d.enc.png) {
-      const EncDesc &e = d.enc;
-      for (uint32_t it = 0; it < e.h; it += 4) b.lists[L_PENC_ROW].push_back({I, it});
-      for (uint32_t it = 0; it < e.nblocks; it += 256) b.lists[L_PENC_PIECE].push_back({I, it});
-      b.lists[L_ENC_IMG].push_back({I, 0});  // k_enc_scan: piece offsets
-      b.lists[L_PENC_IMG].push_back({I, 0});
-    } else if (d.enc.active) {
-      const EncDesc &e = d.enc;
-      for (uint32_t it = 0; it < e.nbx * e.nby; it += 256) b.lists[L_ENC_MCU].push_back({I, it});
-      for (uint32_t it = 0; it < e.nblocks; it += 256) b.lists[L_ENC_BLK].push_back({I, it});
-      b.lists[L_ENC_IMG].push_back({I, 0});
-    }
-  }
-  for (int l = 0; l < L_COUNT; l++) list_hint_[l] = b.lists[l].size();
-  if (entropy_lpt_) {
-    // Entropy workgroups decode a fixed number of bits, but their time follows
-    // the symbol count: images with few coded bits per block (low quality,
-    // flat content: short EOB-heavy codes) run up to 2x the mean.  Dispatch
-    // those first (workgroups start in list order) so they do not form the
-    // kernel's tail.
-    auto cost_sort = [&](std::vector<WgItem> &l) {
-      std::stable_sort(l.begin(), l.end(), [&](const WgItem &x, const WgItem &y) {
-        const ImageDesc &a = b.descs[x.image], &c = b.descs[y.image];
-        return (uint64_t)a.scan_len * c.total_blocks < (uint64_t)c.scan_len * a.total_blocks;
-      });
-    };
-    cost_sort(b.lists[L_SYNC]);
-    cost_sort(b.lists[L_HUFF]);
-  }
-  for (uint32_t j = 0; j < (uint32_t)b.gjobs.size(); j++)
-    for (uint32_t pc = 0; pc * kGatherPiece < b.gjobs[j].len; pc++) b.lists[L_GATHER].push_back({j, pc});
-  if (b.uf_n) {  // unfilter bands in ticket order: the j-th band of every plane, j = 0, 1, ...
-    std::vector<std::vector<uint32_t>> per;  // per PNG image: pass << 24 | band, pass-major
-    std::vector<uint32_t> who;
-    for (uint32_t di = 0; di < (uint32_t)b.descs.size(); di++) {
-      const ImageDesc &d = b.descs[di];
-      if (d.fmt != kFmtPng) continue;
-      std::vector<uint32_t> v;
-      for (uint32_t p = 0; p < (d.png.interlace ? 7u : 1u); p++) {
-        const uint32_t nb = png_pass_bands(d, p);
-        for (uint32_t k = 0; k < nb; k++) v.push_back(p << 24 | k);
-      }
-      per.push_back(std::move(v));
-      who.push_back(di);
-    }
-    for (size_t j = 0, more = 1; more; j++) {
-      more = 0;
-      for (size_t i = 0; i < per.size(); i++)
-        if (j < per[i].size()) {
-          b.lists[L_UNF].push_back({who[i], per[i][j]});
-          more = 1;
-        }
-    }
-  }
-  b.prog_level_n.clear();
-  for (uint32_t j = 0; j < (uint32_t)b.pscans.size(); j++) {  // L_PROG: scans grouped by level
-    const uint32_t lv = b.pscans[j].level;
-    if (lv >= b.prog_level_n.size()) b.prog_level_n.resize(lv + 1, 0);
-    b.prog_level_n[lv]++;
-  }
-  b.prog_dc_n = 0;
-  if (prog_pipe_) {
-    plan_prog_items(b);
-  } else {  // one launch per level: scans grouped by level
-    std::vector<uint32_t> at(b.prog_level_n.size(), 0);
-    for (size_t lv = 1; lv < at.size(); lv++) at[lv] = at[lv - 1] + b.prog_level_n[lv - 1];
-    b.lists[L_PROG].resize(b.pscans.size());
-    for (uint32_t j = 0; j < (uint32_t)b.pscans.size(); j++)
-      b.lists[L_PROG][at[b.pscans[j].level]++] = WgItem{b.pscans[j].image, j};
-  }
-  for (int c = 0; c < 2; c++) {
-    b.decclass[c] = (uint32_t)decl[c].size();
-    b.lists[L_DEC].insert(b.lists[L_DEC].end(), decl[c].begin(), decl[c].end());
-  }
-  for (int c = 0; c < 2; c++) {
-    b.hvclass[c] = (uint32_t)hvl[c].size();
-    b.lists[L_RHV].insert(b.lists[L_RHV].end(), hvl[c].begin(), hvl[c].end());
-  }
-  for (int h = 0; h < 2; h++)
-    for (int f = 1; f >= 0; f--)  // launch order (launch_resize_hm): fused KS 1, KS 2, byte-fill KS 1, KS 2
-      for (int k = 0; k < 2; k++) {
-        b.hmclass[h][f][k] = (uint32_t)hm[h][f][k].size();
-        auto &l = b.lists[h ? L_RM2 : L_RM0];
-        l.insert(l.end(), hm[h][f][k].begin(), hm[h][f][k].end());
-      }
-  for (int h = 0; h < 2; h++)
-    for (int f = 1; f >= 0; f--)  // launch order: fused classes, then byte-fill classes
-      for (int c = 0; c < 4; c++) {
-        b.hclass[h][f][c] = (uint32_t)hb[h][f][c].size();
-        auto &l = b.lists[h ? L_RH2 : L_RH0];
-        l.insert(l.end(), hb[h][f][c].begin(), hb[h][f][c].end());
-      }
-  phase(3);
-  // ---- 6. meta buffer: [flags][descs][lists...]
-  Layout M;
-  b.flags_off = M.take(sizeof(BatchFlags));
-  b.desc_off = M.take(b.descs.size() * sizeof(ImageDesc));
-  for (int l = 0; l < L_COUNT; l++) b.list_off[l] = M.take(b.lists[l].size() * sizeof(WgItem));
-  b.gjob_off = M.take(b.gjobs.size() * sizeof(GatherJob));
-  b.ichunk_off = M.take(b.ichunks.size() * sizeof(InfChunk));
-  b.pscan_off = M.take(b.pscans.size() * sizeof(ProgScan));
-  b.blob_off = M.take(b.blob.size());
-  b.meta_bytes = align_up(M.off, 256);  // the host inputs follow, 16-byte aligned for k_meta_pull
-  st = ensure(sl.meta, b.meta_bytes + 256, sl.st);
-  if (st) return st;
-  for (ImageDesc &d : b.descs) {
-    if (d.fmt == kFmtPng && d.png.pal) d.png.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.png.pal - 1);
-    if (d.enc.active) {
-      d.enc.hdr = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.enc.hdr - 1);
-      d.enc.tab = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + b.enctab_off);
-    }
-  }
-  size_t stage_bytes = b.meta_bytes + (host_io ? IN.off : 0);
-  st = ensure_pinned(sl.stage, stage_bytes + 256, sl.st);
-  if (st) return st;
-  char *P = (char *)sl.stage.p;
-  memset(P + b.flags_off, 0, sizeof(BatchFlags));
-  b.ptime_off = 0;
-  if (wg_timing_) {
-    const size_t nrec = b.lists[L_SYNC].size() + b.lists[L_HUFF].size();
-    b.ptime_off = b.pscans.empty() ? 0 : nrec * 16 + 64;  // per-scan {start, end} after the entropy records
-    st = ensure(sl.wgt, nrec * 16 + 64 + b.pscans.size() * 16, sl.st);
-    if (st) return st;
-    BatchFlags *bf = (BatchFlags *)(P + b.flags_off);
-    bf->wgtime = (uint64_t)(uintptr_t)sl.wgt.p;
-    bf->wgtime_write = (uint32_t)b.lists[L_SYNC].size();
-  }
-  ((BatchFlags *)(P + b.flags_off))->debug = (uint32_t)(debug_flags_ >> 16) & 3u;
-  ((BatchFlags *)(P + b.flags_off))->prio = (uint32_t)entropy_prio_;
-  ((BatchFlags *)(P + b.flags_off))->idct_list = (uint64_t)(uintptr_t)((char *)sl.scratch.p + idct_list_off);
-  ((BatchFlags *)(P + b.flags_off))->idct_cap = b.idct_cap;
-  memcpy(P + b.desc_off, b.descs.data(), b.descs.size() * sizeof(ImageDesc));
-  for (int l = 0; l < L_COUNT; l++)
-    if (!b.lists[l].empty()) memcpy(P + b.list_off[l], b.lists[l].data(), b.lists[l].size() * sizeof(WgItem));
-  if (!b.gjobs.empty()) memcpy(P + b.gjob_off, b.gjobs.data(), b.gjobs.size() * sizeof(GatherJob));
-  if (!b.ichunks.empty()) memcpy(P + b.ichunk_off, b.ichunks.data(), b.ichunks.size() * sizeof(InfChunk));
-  if (!b.pscans.empty()) memcpy(P + b.pscan_off, b.pscans.data(), b.pscans.size() * sizeof(ProgScan));
-  if (!b.blob.empty()) memcpy(P + b.blob_off, b.blob.data(), b.blob.size());
-  if (host_io) {
-    std::vector<CopyJob> ins;
-    for (int i = 0; i < n; i++)
-      if (b.desc_of[i] >= 0) ins.push_back({P + b.meta_bytes + in_off[i], h_srcs[i], lens[i]});
-    parallel_copy(ins, copy_threads_);
-  }
-  last_meta_bytes_ = b.meta_bytes;
-  phase(4);
-  if (timing_) HIPCHK(hipEventRecord(sl.ev[0], sl.st));
-  if (meta_pull_ >= 1) {
-    launch_meta_pull(sl.st, P, sl.meta.p, b.meta_bytes);
-    HIPCHK(hipGetLastError());
-  } else {
-    HIPCHK(hipMemcpyAsync(sl.meta.p, P, b.meta_bytes, hipMemcpyHostToDevice, sl.st));
-  }
-  if (host_io && IN.off) {  // the coded inputs (dg_submit / dg_decode_one)
-    if (meta_pull_ >= 2) {  // off by default: dg_decode_one 18.1 -> 16.6 Gpx/s with it (profiles/r04/one_r4i)
-      launch_meta_pull(sl.st, P + b.meta_bytes, sl.input.p, IN.off);
-      HIPCHK(hipGetLastError());
-    } else {
-      HIPCHK(hipMemcpyAsync(sl.input.p, P + b.meta_bytes, IN.off, hipMemcpyHostToDevice, sl.st));
-    }
-  }
-  b.stage_ms.clear();
-  sl.subs_off = subs_off;  // SubStates and checkpoints live in the scratch arena
-  sl.ckpt_off = ckpt_off;
-  if (host_io) {
-    b.host_outs.assign(outs, outs + n);
-    b.host_caps.assign(caps, caps + n);
-    // outputs into page-locked caller memory go there by DMA, not via the staging buffer
-    for (int i = 0; i < n; i++)
-      if (b.desc_of[i] >= 0 && !b.plans[i].encode && b.plans[i].out_bytes && outs[i] &&
-          host_pinned(outs[i], b.plans[i].out_bytes))
-        b.out_direct[i] = 1;
-  }
-  sl.batch = std::move(bp);
-  croll.armed = false;
-  phase(5);
-  st = launch_all(sl, false);
-  if (st) {
-    fail_batch(sl, st);
-    return st;
-  }
-  phase(6);
-  stat_batches_++;
-  *ticket = sl.batch->ticket;
-  if ((!max_dev_bytes_ || budget_planned_) && stat_batches_ <= 2 * kMaxInflight) prewarm_slots(sl);
-  return DG_OK;
 }
 
 // The first batches (no budget): the idle baseline slots in turn take the

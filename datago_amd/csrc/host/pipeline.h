@@ -189,6 +189,12 @@ struct RecentTab {
   int idx = -1;
 };
 
+// The batch planner's own types (submit.cpp).
+struct SubmitArgs;
+struct BatchLayout;
+struct Offs;
+struct ClassLists;
+
 class Context {
  public:
   Context(int device, const dg_image_config *cfg);
@@ -231,6 +237,28 @@ class Context {
   int timings(const char **names, float *ms, int cap);
 
  private:
+  // submit()'s phases, in the order they run (submit.cpp)
+  dg_status wait_slot(Slot &sl, std::unique_lock<std::mutex> &lk);  // the slot's previous batch; unlocks while it waits
+  void plan_images(const SubmitArgs &a, Batch &b);
+  dg_status pool_tables(Batch &b);
+  void choose_sub_bits(const Batch &b, BatchLayout &bl);
+  void layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl);  // per image: the next five
+  void layout_png(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  void layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  void layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  int plan_resize(const ImagePlan &p, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  void layout_output_and_encode(const SubmitArgs &a, int i, int last_stage, Batch &b, BatchLayout &bl, ImageDesc &d,
+                                Offs &o);
+  void layout_batch_regions(Batch &b, BatchLayout &bl);
+  dg_status fit_device(Slot &sl, const Batch &b, const BatchLayout &bl);
+  void patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const BatchLayout &bl);  // per image: the next three
+  void patch_jpeg(const JpegHeader &h, const uint8_t *src, const Slot &sl, const Offs &o, int di, Batch &b);
+  void prog_scan_records(const JpegHeader &h, const uint8_t *src, int di, Batch &b);
+  void patch_passes(char *S, const Offs &o, int di, Batch &b);
+  void build_lists(Batch &b);
+  void image_items(int di, Batch &b, ClassLists &cl);
+  dg_status stage_and_upload(const SubmitArgs &a, Slot &sl, Batch &b, const BatchLayout &bl);
+  dg_status enqueue_upload(const SubmitArgs &a, Slot &sl, Batch &b, const BatchLayout &bl);
   dg_status plan_image(const uint8_t *h, size_t len, int32_t forced, ImagePlan &p);
   int pool_huff(const HuffSpec &s);
   dg_status flush_pools();
@@ -307,6 +335,7 @@ class Context {
   int64_t stat_ccache_hits_ = 0, stat_ccache_new_ = 0, stat_ccache_resets_ = 0;
   int ccache_lookup(const ResizePass &ps, Batch &b, bool &hit);  // mu_ held; -1 = not cached
   void ccache_maybe_reset(Slot &self);                            // mu_ held, before a batch's lookups
+  void ccache_clear(bool free_arena);                             // mu_ held, no batch in flight uses the cache
   void ccache_rollback(size_t n0, size_t off0);                   // a submit that installs no batch
   size_t max_dev_bytes_ = 0;        // option "max_device_mb" (0: no budget)
   size_t budget_room_ = 0;          // headroom the current submit's growth may take under the budget
