@@ -40,9 +40,10 @@ DG_HD uint32_t bswap32(uint32_t x) {
 // ahead, issued whenever a lane crossed a word -- stalled the wave on nearly
 // every symbol: a wave has one in-order load counter, so the wait for the
 // word a lane loaded symbols ago also waited for the loads other lanes had
-// issued since.  One symbol consumes at most 31 bits, so with pos - base < 32
-// before a symbol at most one 32-bit shift follows it, and a lane with a
-// non-empty buffer at the start of a step never runs dry within it.
+// issued since.  One symbol consumes at most 31 bits and a multi-symbol step
+// at most the 32 of its peek, so with pos - base < 32 before a step at most
+// one 32-bit shift follows it, and a lane with a non-empty buffer at the
+// start of a step never runs dry within it.
 // Destuffed streams are stored word-interleaved across groups of 64
 // subsequences: logical 32-bit word w of subsequence s = w >> lsw (2^lsw
 // words per subsequence) sits in row (s / 64) * 2^lsw + (w mod 2^lsw),
@@ -205,6 +206,57 @@ DG_HD uint32_t multi_next_z(uint32_t m, uint32_t z) {
   const uint32_t c = m & 15u, adv = (m >> 4) & 127u, eob = (m >> 11) & 1u;
   const bool ok = c != 0u && z != 0u && (eob ? z + adv < 64u : z + adv <= 64u);
   return ok ? (eob ? 64u : z + adv) : 0xFFFFFFFFu;
+}
+
+// Step accounting of the state-only decodes for the CPU emulators (a test
+// defines DG_STEP_STATS before including this file; never on the device, so
+// the kernels' registers are untouched): loop iterations of lead_in and of
+// decode_range<false>, chained multi entries taken, and steps that consumed
+// more than the 32 bits one bw_shift covers (must stay 0).
+#if defined(DG_STEP_STATS) && !defined(DG_DEVICE)
+struct StepStats {
+  uint64_t lead_steps, range_steps, chained, over32;
+};
+inline StepStats g_step_stats = {0, 0, 0, 0};
+#define DG_STEP_STAT(field, n) (g_step_stats.field += (n))
+#else
+#define DG_STEP_STAT(field, n) ((void)0)
+#endif
+
+// Chained multi steps (option "sync_chain"): after the first action of a
+// state-only step -- one symbol, or a multi entry -- up to `chain` more multi
+// entries of the same block are taken out of the same 32-bit peek.  The fixed
+// part of a step (event compare, refill ballot, peek, bw_shift, block and
+// table bookkeeping) is most of its cost, so fewer, longer steps are cheaper
+// than the table reads they add.  Entry x is taken when the block is still
+// open (multi_next_z rejects zn == 64 and runs that leave the block), it ends
+// at or before the next event -- the rule of the first entry, so the first
+// symbol boundary at or after every event is still visited -- and it lies
+// inside the peek: `used` bits are gone, the index is the next kMultiBits of
+// what is left (zeros shifted in: an entry reaching into them is rejected
+// whole by used + c <= 32).  A step still consumes at most 32 bits, which is
+// what its single bw_shift requires.  Slots only add to pos; a rejected slot
+// leaves the state as it was, so the slots after it reject the same entry.
+// DG_CHAIN_DC 1 lets a DC step chain too, after its single symbol (0 / 1
+// measured with two chained entries: huff_sync 1.35-1.41 / 1.12-1.15 ms).
+#ifndef DG_CHAIN_DC
+#define DG_CHAIN_DC 1
+#endif
+DG_HD void multi_chain(const uint16_t *mt, uint32_t mi, uint32_t bits, uint32_t chain, bool open, uint32_t ev,
+                       uint32_t &used, uint32_t &pos, uint32_t &zn) {
+#pragma unroll
+  for (uint32_t x = 0; x < 3u; x++) {
+    if (x >= chain) break;
+    const uint32_t bx = used < 32u ? bits << used : 0u;
+    const uint32_t m = (open && mi != 3u) ? (uint32_t)mt[(mi << kMultiBits) | (bx >> (32u - kMultiBits))] : 0u;
+    const uint32_t c = m & 15u;
+    const uint32_t zx = multi_next_z(m, zn);
+    const bool tk = zx != 0xFFFFFFFFu && pos + c <= ev && used + c <= 32u;
+    pos += tk ? c : 0u;
+    used += tk ? c : 0u;
+    zn = tk ? zx : zn;
+    DG_STEP_STAT(chained, tk ? 1u : 0u);
+  }
 }
 
 // Accumulators of one subsequence decode.
@@ -542,7 +594,7 @@ DG_HD uint32_t first_marker(const DG_GLOBAL uint32_t *mk, uint32_t nmk, uint32_t
 template <class TAB>
 DG_HD uint32_t lead_in(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL uint8_t *stream,
                        const DG_GLOBAL uint32_t *mk, uint32_t s, uint32_t lead,
-                       const uint16_t *mt = nullptr, uint32_t acm = 0xFFu, bool pair = false) {
+                       const uint16_t *mt = nullptr, uint32_t acm = 0xFFu, bool pair = false, uint32_t chain = 0) {
   const uint32_t a0 = s * im.sub_bits;
   if (s == 0 || lead == 0 || a0 >= im.ds_bits) return pack_state(0, 0, 0);
   uint32_t pos = a0 > lead ? a0 - lead : 0u;
@@ -583,6 +635,7 @@ DG_HD uint32_t lead_in(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL uin
     const uint32_t zm = multi_next_z(m, z);
     const uint32_t lim = a0 < mpos ? a0 : mpos;
     const bool take_m = zm != 0xFFFFFFFFu && pos + (m & 15u) <= lim;
+    const uint32_t p0 = pos;
     pos += take_m ? (m & 15u) : (e >> 8) + (sym & 15u);
     uint32_t zn = take_m ? zm : huff_next_z(z, sym);
     if (pair && !take_m) {  // a second AC symbol from the same peek (see decode_range)
@@ -596,6 +649,12 @@ DG_HD uint32_t lead_in(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL uin
         zn = huff_next_z(zn, sym2);
       }
     }
+    if (chain) {  // further multi entries of the block out of the same peek
+      uint32_t used = pos - p0;
+      multi_chain(mt, mi, bits, chain, DG_CHAIN_DC || z != 0u, lim, used, pos, zn);
+    }
+    DG_STEP_STAT(lead_steps, 1u);
+    DG_STEP_STAT(over32, pos - p0 > 32u ? 1u : 0u);
     bw_shift(b, pos);
     const bool bend = zn >= 64u;
     z = bend ? 0u : zn;
@@ -620,7 +679,7 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
                         uint32_t s, uint32_t in, RangeAcc &acc, WriteCtx *w, DG_GLOBAL Ckpt *ck = nullptr,
                         bool merge = false, uint32_t old_out = 0, StageCtx *stg = nullptr,
                         const uint16_t *mt = nullptr, uint32_t acm = 0xFFu, uint32_t pair = 0,
-                        uint32_t a0o = kInf, uint32_t a1o = kInf) {
+                        uint32_t a0o = kInf, uint32_t a1o = kInf, uint32_t chain = 0) {
   // [a0o, a1o): a part of the range (k_huff_write's split halves); `in` is
   // then the state at the first symbol boundary at/after a0o
   const uint32_t S = im.sub_bits, total = im.ds_bits;
@@ -759,6 +818,7 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
       zm = pos + mc <= ev ? multi_next_z(m, z) : 0xFFFFFFFFu;
     }
     const bool take_m = zm != 0xFFFFFFFFu;
+    const uint32_t p0 = pos;
     pos += take_m ? mc : len + size;
     const int32_t vdc = isdc ? v : 0;
     acc.n += isdc ? 1u : 0u;
@@ -813,7 +873,15 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
         open = tk && !(zx == 0u && (sx >> 4) != 15u);
       }
     }
-    bw_shift(b, pos);  // one shift: both symbols came out of one peek (< 32 bits past it)
+    if (!WRITE && chain) {  // state-only: further multi entries of the block out of the same peek
+      uint32_t used = pos - p0;
+      multi_chain(mt, mi, bits, chain, DG_CHAIN_DC || !isdc, ev, used, pos, zn);
+    }
+    if (!WRITE) {
+      DG_STEP_STAT(range_steps, 1u);
+      DG_STEP_STAT(over32, pos - p0 > 32u ? 1u : 0u);
+    }
+    bw_shift(b, pos);  // one shift: everything taken came out of one peek (<= 32 bits past it)
     const bool bend = zn >= 64u;
     if (WRITE && bend) wc_end_block<COOP>(*w, pending);
     z = bend ? 0u : zn;

@@ -471,6 +471,11 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     sync_pair_ = v != 0;
     return DG_OK;
   }
+  if (k == "sync_chain") {  // k_huff_sync: up to v more multi entries per state-only step from the same peek (0..3)
+    if (v < 0 || v > 3) return opt_error(k, v, "valid unless v < 0 || v > 3");
+    sync_chain_ = (int)v;
+    return DG_OK;
+  }
   if (k == "write_pair") {  // k_huff_write: up to v more AC symbols per step from the same peek (0..3)
     if (v < 0 || v > 3) return opt_error(k, v, "valid unless v < 0 || v > 3");
     write_pair_ = (int)v;
@@ -701,6 +706,7 @@ int64_t Context::get_stat(const std::string &k) {
   if (k == "prog_chains") return stat_prog_chains_;
   if (k == "pool_flushes") return stat_pool_flush_;
   if (k == "sync_iters_max") return stat_iters_;
+  if (k == "sync_chain") return sync_chain_;
   {  // wg_timing summaries, in nanoseconds: wg_{sync,write}_{span,mean,p90,max}
     static const char *kn[2] = {"sync", "write"}, *sn[4] = {"span", "mean", "p90", "max"};
     for (int a = 0; a < 2; a++)
@@ -1707,7 +1713,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   Ckpt *ck = (Ckpt *)((char *)sl.scratch.p + sl.ckpt_off);
   if (!from_fix)
     launch_huff_sync(sl.st, dd, lst(L_SYNC), cnt(L_SYNC), hp, subs, ck, fl, b.stage_on, b.max_slots,
-                     multi_lead_ ? b.max_ac : 0u, sync_pair_, sync2_);
+                     multi_lead_ ? b.max_ac : 0u, sync_pair_, sync2_, (uint32_t)sync_chain_);
   if (next()) return DG_ERR_DEVICE;
   launch_huff_fix(sl.st, dd, lst(L_SYNC), cnt(L_SYNC), hp, subs, ck, fl, b.stage_on, b.max_slots);
   if (next()) return DG_ERR_DEVICE;

@@ -426,6 +426,7 @@ class Context {
   bool multi_lead_ = true;   // option "multi_lead": multi-symbol AC steps in k_huff_sync's state-only decodes
   int write_pair_ = 3;       // option "write_pair": up to this many more AC symbols per k_huff_write step from one peek
   bool sync2_ = false;       // option "sync2": k_huff_sync with two chains per lane (k_huff_sync2)
+  int sync_chain_ = 2;       // option "sync_chain": up to this many more multi entries per k_huff_sync step from one peek
   bool sync_pair_ = false;   // option "sync_pair": the same in k_huff_sync (measured slower beside multi_lead: off)
   bool prog_side_ = false;  // option "prog_side": progressive scans on the side stream (measured slower: off)
   int coalesce_max_ = 64, coalesce_us_ = 500;

@@ -16,10 +16,11 @@ void launch_destuff_one(hipStream_t st, ImageDesc *imgs, const WgItem *list, uin
 struct Ckpt;
 // stage: decode-once staging (ImageDesc::stage), see k_huff_scatter
 // max_slots: the largest ImageDesc::nslots in the batch (dynamic LDS for the tables);
-// max_ac: the most distinct AC tables of an image (multi-symbol lead-in lookups, 0 = off)
+// max_ac: the most distinct AC tables of an image (multi-symbol lead-in lookups, 0 = off);
+// chain: further multi entries per state-only step of k_huff_sync (0..3, option "sync_chain")
 void launch_huff_sync(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                       const HuffTable *pool, SubState *subs, Ckpt *ck, BatchFlags *flags, bool stage,
-                      uint32_t max_slots, uint32_t max_ac, bool pair, bool two = false);
+                      uint32_t max_slots, uint32_t max_ac, bool pair, bool two = false, uint32_t chain = 0);
 void launch_huff_fix(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                      const HuffTable *pool, SubState *subs, Ckpt *ck, BatchFlags *flags, bool stage,
                      uint32_t max_slots);

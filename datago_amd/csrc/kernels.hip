@@ -502,11 +502,12 @@ __global__ __launch_bounds__(256) void k_huff_sync(const ImageDesc *__restrict__
   RangeAcc acc = {0, 0, 0, {0, 0, 0}};
   // entry state: exact for s == 0, otherwise the lead-in decode's guess
   const bool pair = (multi & 2u) != 0;
-  uint32_t in = active ? lead_in(im, tabs, scan, mkp, s, im.lead_bits, (multi & 1u) ? mt : nullptr, acm, pair)
+  const uint32_t chain = (multi & 1u) ? (multi >> 2) & 3u : 0u;  // chained multi entries per step (multi_chain)
+  uint32_t in = active ? lead_in(im, tabs, scan, mkp, s, im.lead_bits, (multi & 1u) ? mt : nullptr, acm, pair, chain)
                        : pack_state(0, 0, 0);
   if (active)
     decode_range<false>(im, tabs, scan, mkp, s, in, acc, nullptr, ck, false, 0, stg, (multi & 1u) ? mt : nullptr, acm,
-                        pair);
+                        pair, kInf, kInf, chain);
   ex[t] = active ? acc.out : 0u;
   ins[t] = in;
   __syncthreads();
@@ -517,7 +518,7 @@ __global__ __launch_bounds__(256) void k_huff_sync(const ImageDesc *__restrict__
     __syncthreads();
     if (redo) {
       decode_range<false>(im, tabs, scan, mkp, s, pin, acc, nullptr, ck, true, ex[t], stg, (multi & 1u) ? mt : nullptr,
-                          acm, pair);
+                          acm, pair, kInf, kInf, chain);
       ex[t] = acc.out;
       ins[t] = pin;
     }
@@ -3251,10 +3252,11 @@ void launch_destuff_one(hipStream_t st, ImageDesc *imgs, const WgItem *list, uin
 // per workgroup, 8 resident workgroups per CU instead of 6
 void launch_huff_sync(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                       const HuffTable *pool, SubState *subs, Ckpt *ck, BatchFlags *flags, bool stage,
-                      uint32_t max_slots, uint32_t max_ac, bool pair, bool two) {
+                      uint32_t max_slots, uint32_t max_ac, bool pair, bool two, uint32_t chain) {
   if (!nwg) return;
   const size_t lds = (size_t)max_slots * sizeof(HuffTable) + ((size_t)max_ac << kMultiBits) * 2;
-  const uint32_t multi = (max_ac ? 1u : 0u) | (pair ? 2u : 0u);  // bit 0: multi-symbol lookups, bit 1: pair steps
+  // bit 0: multi-symbol lookups, bit 1: pair steps, bits 2-3: chained multi entries per step (k_huff_sync)
+  const uint32_t multi = (max_ac ? 1u : 0u) | (pair ? 2u : 0u) | ((chain & 3u) << 2);
   if (two && !stage && !pair)  // two chains per lane (k_huff_sync2: no staging, no pair steps)
     hipLaunchKernelGGL(k_huff_sync2, dim3(nwg), dim3(128), lds, st, imgs, list, pool, subs, ck, flags, multi);
   else if (stage)
