@@ -325,7 +325,8 @@ class Context:
     def __init__(self, device: int = 0, crop_and_resize: bool = False, default_image_size: int = 0,
                  downsampling_ratio: int = 0, min_aspect_ratio: float = 0.0, max_aspect_ratio: float = 0.0,
                  image_to_rgb8: bool = False, pre_encode_images: bool = False, encode_format: int = 0,
-                 jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False):
+                 jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False,
+                 resize16: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -342,6 +343,8 @@ class Context:
         self.buckets = BucketTable(0, 0, 0, 0, _borrowed=bt) if bt else None
         if png16:  # 16-bit PNGs decode on the GPU (uint16 arrays / tensors); off: DG_ERR_UNSUPPORTED
             self.set_option("png16", 1)
+        if resize16:  # ... and those that are not their bucket's size resize to it (with png16)
+            self.set_option("resize16", 1)
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

@@ -27,6 +27,7 @@ SOURCES = [
     ("dg_prog.hip", True),
     ("dg_penc.hip", True),
     ("dg_band.hip", True),
+    ("dg_resize16.hip", True),
     ("host/jpeg_enc.cpp", False),
     ("host/wds.cpp", False),
     ("host/png_header.cpp", False),

@@ -102,11 +102,13 @@ struct ResizePass {
   uint32_t bands;           // band H kernel: kHBandRows-row bands per workgroup (option "hb_bands")
   uint32_t row0;            // H pass: first source row; V pass: source row of temp row 0
   uint32_t C;               // channels
-  uint32_t kind;            // 0 none, 1 horizontal, 2 vertical
+  uint32_t kind;            // 0 none, 1 horizontal, 2 vertical; kR16V / kR16H: the 16-bit resize's passes
+                            // (option "resize16", dg_resize16.hip: f32 weights in coef, {left, count} in bounds)
   uint32_t mode;            // H passes: kHFused = source is the YCbCr planes (upsample + colour
                             // in the fill), kHDirect = segment too wide for LDS (legacy kernel)
 };
 constexpr uint32_t kHFused = 1, kHDirect = 2;
+constexpr uint32_t kR16V = 3, kR16H = 4;  // ResizePass::kind of pass[0] / pass[1] of a resized 16-bit PNG
 constexpr uint32_t kHVFused = 4;      // pass[0] runs fused with pass[1] in k_resize_hv (its H rows stay in LDS)
 // pass[0] of a JPEG runs in k_band_dec (dg_band.hip): IDCT + upsampling + colour + this H pass from the
 // coefficients, 16-row strips of kDecCols output columns; kHDecWide: the 640-pixel segment class

@@ -394,6 +394,16 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     png16_ = v != 0;
     return DG_OK;
   }
+  if (k == "resize16") {
+    // 16-bit PNGs that are not their bucket's size (default off:
+    // DG_ERR_UNSUPPORTED).  1, together with "png16": they resize with the
+    // image crate's resize_to_fill(Lanczos3), which the reference uses for
+    // every non-U8 pixel type (dg_resize16.h); 16-bit into an encoder stays
+    // DG_ERR_UNSUPPORTED.
+    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
+    resize16_ = v != 0;
+    return DG_OK;
+  }
   if (k == "prog_lanes") {  // dg_decode_one: progressive batches in flight on the progressive slots; 0: mixed in
     if (v < 0 || v > kProgSlots) return opt_error(k, v, "valid unless v < 0 || v > " + std::to_string(kProgSlots));
     prog_lanes_ = (int)v;
@@ -1293,6 +1303,46 @@ dg_status Context::upload_pools() {
   return DG_OK;
 }
 
+// The 16-bit resize of a W x H x C image to its ow x oh bucket (option
+// "resize16"): resize_to_fill's geometry, the tap counts of both passes and
+// the samples of a decoded row that the f32 intermediate holds -- it covers
+// the crop window's rows and the columns the cropped outputs' taps read.
+// False (p.png.why set) where the GPU path does not take the image.
+static bool plan_r16(uint32_t W, uint32_t H, uint32_t C, uint32_t ow, uint32_t oh, ImagePlan &p) {
+  p.r16 = true;
+  if (!r16_geom(W, H, ow, oh, p.r16g)) {
+    p.png.why = "PNG: 16-bit resize whose scaled size does not cover the bucket";
+    return false;
+  }
+  const R16Geom &g = p.r16g;
+  p.r16_passes = !(g.w2 == W && g.h2 == H);
+  if (!p.r16_passes) return true;  // a pure crop: the source's own samples
+  int32_t cmin = (int32_t)W, cmax = 0, kh = 0, kv = 0;
+  for (uint32_t x = 0; x < ow; x++) {
+    const R16Window b = r16_window(W, g.w2, g.x0 + x);
+    cmin = std::min(cmin, b.left);
+    cmax = std::max(cmax, b.right);
+    kh = std::max(kh, b.right - b.left);
+  }
+  for (uint32_t y = 0; y < oh; y++) {
+    const R16Window b = r16_window(H, g.h2, g.y0 + y);
+    kv = std::max(kv, b.right - b.left);
+  }
+  // whole quads of samples (k_r16_v: 8 bytes in, 16 out per lane); the decoded
+  // row's stride is a multiple of 8 samples, so the last quad stays inside it
+  p.r16_s0 = ((uint32_t)cmin * C) & ~3u;
+  p.r16_ns = (uint32_t)align_up((size_t)cmax * C, 4) - p.r16_s0;
+  p.r16_kv = (uint32_t)kv;
+  p.r16_kh = (uint32_t)kh;
+  // the intermediate and the tap tables stay 32-bit addressable, like the decoder's working set
+  if ((uint64_t)p.r16_ns * 4 * oh >= (1ull << 31) || (uint64_t)oh * p.r16_kv * 4 >= (1ull << 31) ||
+      (uint64_t)ow * p.r16_kh * 4 >= (1ull << 31)) {
+    p.png.why = "PNG: 16-bit resize whose f32 intermediate is too large for the GPU path";
+    return false;
+  }
+  return true;
+}
+
 // Decide what the GPU will do with one image: header, bucket, output size.
 dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, ImagePlan &p) {
   p = ImagePlan();
@@ -1377,9 +1427,15 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
   if (deep && has_cfg_ && !(W == ow && H == oh)) {
     // the reference resizes non-U8 pixel types with image's own f32 Lanczos3
     // (resize_to_fill), not the fast_image_resize path restated here
-    p.png.why = "PNG: 16-bit resize (only a 16-bit image of its bucket's size decodes on the GPU)";
-    p.status = DG_ERR_UNSUPPORTED;
-    return DG_OK;
+    if (!resize16_) {
+      p.png.why = "PNG: 16-bit resize (only a 16-bit image of its bucket's size decodes on the GPU)";
+      p.status = DG_ERR_UNSUPPORTED;
+      return DG_OK;
+    }
+    if (!plan_r16(W, H, C, ow, oh, p)) {
+      p.status = DG_ERR_UNSUPPORTED;
+      return DG_OK;
+    }
   }
   if (deep && cfg_.pre_encode_images && !cfg_.image_to_rgb8) {
     p.png.why = "PNG: 16-bit image to an encoder (the GPU encoders take 8-bit samples)";
@@ -1616,6 +1672,13 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   // decoded images themselves (PNG, alpha programs on them) are not redone
   const int alpha_flags = from_fix ? 1 : 0;
   if (next()) return DG_ERR_DEVICE;
+  if (!from_fix && cnt(L_R16T)) {  // 16-bit resize: tap tables depend only on the plan (beside the inflate / unfilter)
+    if (side_stream_) {
+      HIPCHK(hipEventRecord(sl.ev_meta, sl.st));
+      HIPCHK(hipStreamWaitEvent(sl.side, sl.ev_meta, 0));
+    }
+    launch_r16_taps(side_stream_ ? sl.side : sl.st, dd, lst(L_R16T), cnt(L_R16T));
+  }
   if (!from_fix && b.any_png) {
     launch_png_gather(sl.st, (const GatherJob *)(M + b.gjob_off), lst(L_GATHER), cnt(L_GATHER));
     if (!b.ichunks.empty()) {
@@ -1741,9 +1804,11 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   launch_resize_hb(sl.st, dd, lst(L_RH0), b.hclass[0], 0, h_prefetch_, h_planar_, b.h_zune != 0);
   launch_resize_hv(sl.st, dd, lst(L_RHV), b.hvclass);
   launch_resize_h(sl.st, dd, lst(L_RHX0), cnt(L_RHX0), 0 | ((debug_flags_ & 0xFF) << 8));
+  if (!from_fix) launch_r16_v(sl.st, dd, lst(L_R16V), cnt(L_R16V));  // (PNG only: nothing a resync round redoes)
   if (next()) return DG_ERR_DEVICE;
   launch_resize_v(sl.st, dd, lst(L_RV1), cnt(L_RV1), 1, v_units_);
   launch_resize_vt(sl.st, dd, lst(L_RVT1), cnt(L_RVT1), 1, b.v_tile);
+  if (!from_fix) launch_r16_h(sl.st, dd, lst(L_R16H), cnt(L_R16H));
   launch_alpha(sl.st, dd, lst(L_ALPHA1), cnt(L_ALPHA1), 1 | (alpha_flags << 8));
   if (next()) return DG_ERR_DEVICE;
   launch_resize_hm(sl.st, dd, lst(L_RM2), b.hmclass[1], 2);

@@ -12,6 +12,7 @@
 
 #include "../../../include/datago_hip.h"
 #include "../dg_types.h"
+#include "../dg_resize16.h"
 #include "buckets.h"
 #include "jpeg_header.h"
 #include "png_header.h"
@@ -44,6 +45,12 @@ struct ImagePlan {
   bool enc_png = false;    // encode_format png (dg_penc.hip)
   bool enc_la_gray = false;  // resized LA: encoded as the GrayImage over its bytes
   uint64_t img_bytes = 0;  // transformed image bytes (out_w * out_h * out_c, x 2 at bit_depth 16)
+  // 16-bit resize (option "resize16", dg_resize16.h): the image crate's resize_to_fill
+  bool r16 = false;          // a 16-bit PNG that is not its bucket's size
+  bool r16_passes = false;   // ... and whose intermediate differs from the source (else a pure crop)
+  R16Geom r16g = {0, 0, 0, 0};
+  uint32_t r16_s0 = 0, r16_ns = 0;  // samples of a decoded row the intermediate holds: first, count (x 4)
+  uint32_t r16_kv = 0, r16_kh = 0;  // weight slots per table entry of the V / H pass (the largest tap count)
 };
 
 // The completion event of one batch (shared with waiters, so a slot recycled
@@ -64,8 +71,8 @@ struct Batch {
   std::vector<ImageDesc> descs;
   std::vector<int> desc_of;           // image -> desc index or -1
   // workgroup lists (host copies) and their offsets in the device meta buffer
-  std::vector<WgItem> lists[40];
-  size_t list_off[40] = {0};
+  std::vector<WgItem> lists[48];
+  size_t list_off[48] = {0};
   // PNG: IDAT gather jobs and palettes, uploaded with the descriptors
   std::vector<GatherJob> gjobs;
   size_t gjob_off = 0;
@@ -178,9 +185,10 @@ enum ListId {
   L_RM0, L_RM2,                                             // band H passes on the matrix cores (k_resize_hm)
   L_RVT1, L_RVT3,                                           // V passes on column tiles (k_resize_vt)
   L_EXPAND16,                                               // 16-bit PNG sample step (k_png_expand16)
+  L_R16T, L_R16V, L_R16H,                                   // 16-bit resize: tap tables, V pass, H pass (dg_resize16.hip)
   L_COUNT
 };
-static_assert((int)L_COUNT <= 40, "Batch::lists");
+static_assert((int)L_COUNT <= 48, "Batch::lists");
 
 // A recently pooled table (pool_huff / pool_quant): its key bytes and slot.
 struct RecentTab {
@@ -247,6 +255,7 @@ class Context {
   void layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   int plan_resize(const ImagePlan &p, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  int plan_resize16(const ImagePlan &p, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_output_and_encode(const SubmitArgs &a, int i, int last_stage, Batch &b, BatchLayout &bl, ImageDesc &d,
                                 Offs &o);
   void layout_batch_regions(Batch &b, BatchLayout &bl);
@@ -513,6 +522,7 @@ class Context {
   bool idct_fused_ = false;             // option "idct_fused" (measured 7x slower k_huff_write: off)
   bool progressive_ = true;             // option "progressive"
   bool png16_ = false;                  // option "png16": 16-bit PNGs decode on the GPU
+  bool resize16_ = false;               // option "resize16": ... and resize to their bucket (dg_resize16.hip)
   bool prog_serial_ = false;            // option "prog_serial": serial reader for every scan (A/B)
   bool prog_pipe_ = true;               // option "prog_pipe": all scans in one pipelined launch (0: one launch per level)
   int prog_chain_ = 100;                // option "prog_chain": chain dependency groups costing <= this % of the longest scan

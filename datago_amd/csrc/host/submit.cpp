@@ -671,6 +671,7 @@ int Context::plan_resize(const ImagePlan &p, Batch &b, BatchLayout &bl, ImageDes
   d.out_h = p.out_h;
   d.out_c = p.out_c;
   d.out_stride = p.out_w * p.out_c * (p.bit_depth == 16 ? 2 : 1);
+  if (p.r16) return plan_resize16(p, bl, d, o);  // 16-bit PNG (option "resize16"): the image crate's f32 passes
   uint32_t cw = W, chh = H;     // extent of the current image's valid window
   uint32_t xoff = 0, yoff = 0;  // window origin (pixels, rows) inside the current buffer
   int last_stage = -1;
@@ -799,13 +800,70 @@ int Context::plan_resize(const ImagePlan &p, Batch &b, BatchLayout &bl, ImageDes
   return last_stage;
 }
 
+// The passes of a 16-bit PNG that is not its bucket's size (dg_resize16.h):
+// pass[0] = the vertical pass into the f32 intermediate, pass[1] = the
+// horizontal pass; the integer centre crop folds into both (out0, and the
+// sample window [r16_s0, + r16_ns) of the intermediate's rows).  The tap
+// tables sit in the early region (k_r16_taps runs beside the inflate), the
+// intermediate in the late one.  No alpha programs: the crate's resize does
+// not premultiply.  Returns the last pass's stage (-1: a pure crop).
+int Context::plan_resize16(const ImagePlan &p, BatchLayout &bl, ImageDesc &d, Offs &o) {
+  const uint32_t W = d.width, H = d.height, C = d.dec_c;
+  const R16Geom &g = p.r16g;
+  if (!p.r16_passes) {  // the intermediate is the source: k_copy reads the centre window
+    o.final_off = (size_t)g.y0 * d.pix_stride + (size_t)g.x0 * C * 2;
+    return -1;
+  }
+  auto tables = [&](int stage, uint32_t entries, uint32_t ksize) {
+    o.pass_coef[stage] = bl.L.take((size_t)entries * ksize * 4);
+    o.pass_bounds[stage] = bl.L.take((size_t)entries * 8);
+  };
+  ResizePass &v = d.pass[0];
+  v.kind = kR16V;
+  v.in_size = H;
+  v.out_size = g.h2;
+  v.out0 = g.y0;
+  v.ksize = p.r16_kv;
+  v.src_stride = d.pix_stride;
+  v.dst_stride = p.r16_ns * 4;  // whole 16-byte units (r16_ns is a multiple of 4)
+  v.width = p.r16_ns;           // samples per intermediate row
+  v.rows = p.out_h;
+  v.row0 = p.r16_s0;
+  v.C = C;
+  o.pass_srcoff[0] = (size_t)p.r16_s0 * 2;
+  o.pass_dst[0] = bl.late().take((size_t)v.dst_stride * v.rows);
+  o.late |= bl.alias ? 8u : 0u;
+  tables(0, v.rows, v.ksize);
+  ResizePass &h = d.pass[1];
+  h.kind = kR16H;
+  h.in_size = W;
+  h.out_size = g.w2;
+  h.out0 = g.x0;
+  h.ksize = p.r16_kh;
+  h.src_stride = v.dst_stride;
+  h.dst_stride = (uint32_t)align_up((size_t)p.out_w * C * 2, 16);
+  h.width = p.out_w;
+  h.rows = p.out_h;
+  h.row0 = p.r16_s0;  // the intermediate's first sample (of a decoded row)
+  h.C = C;
+  if (p.bit_depth == 16) {
+    o.pass_dst[1] = (size_t)-1;  // straight into the output (layout_output_and_encode)
+  } else {                       // image_to_rgb8: k_copy mode 6 reads the resized samples
+    o.pass_dst[1] = bl.late().take((size_t)h.dst_stride * h.rows);
+    o.late |= bl.alias ? 16u : 0u;
+  }
+  tables(1, h.width, h.ksize);
+  return 1;
+}
+
 void Context::layout_output_and_encode(const SubmitArgs &a, int i, int last_stage, Batch &b, BatchLayout &bl,
                                        ImageDesc &d, Offs &o) {
   const ImagePlan &p = b.plans[i];
   const uint32_t W = d.width, H = d.height, C = d.dec_c;
   // final write: the last pass writes straight into the output when the
   // channel count is unchanged; otherwise (or with no pass) k_copy runs.
-  if (last_stage >= 0 && d.out_c == C) {
+  // (16-bit samples under image_to_rgb8 always go through k_copy's 16-to-8 conversion)
+  if (last_stage >= 0 && d.out_c == C && !(d.sample_bytes == 2 && p.bit_depth != 16)) {
     d.pass[last_stage].dst_stride = d.out_stride;
     o.pass_dst[last_stage] = (size_t)-1;  // -> out
     d.copy_needed = 0;
@@ -813,7 +871,7 @@ void Context::layout_output_and_encode(const SubmitArgs &a, int i, int last_stag
     d.copy_needed = 1;
     d.final_src_c = C;
     d.final_src_stride = last_stage >= 0 ? d.pass[last_stage].dst_stride : decoded_stride(d);
-    if (d.sample_bytes == 2)  // 16-bit PNG (never resized: plan_image): u16 copy, or to_rgb8
+    if (d.sample_bytes == 2)  // 16-bit PNG (a bucket's size, a pure crop or the resized samples): u16 copy, or to_rgb8
       d.copy_mode = p.bit_depth == 16 ? 5 : 6;
     else if (d.out_c == C)
       d.copy_mode = 0;
@@ -1293,6 +1351,15 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
   for (int s = 0; s < kStages; s++) {
     const ResizePass &ps = d.pass[s];
     if (!ps.kind) continue;
+    if (ps.kind == kR16V || ps.kind == kR16H) {  // 16-bit resize (dg_resize16.hip)
+      const bool vp = ps.kind == kR16V;
+      const uint32_t entries = vp ? ps.rows : ps.width;
+      for (uint32_t j = 0; j < entries; j += 256) b.lists[L_R16T].push_back({I, (uint32_t)s << 31 | j});
+      // one workgroup per 256 sample quads (V) / 256 output pixels (H) of a row
+      const uint32_t cnt = ps.rows * (((vp ? ps.width / 4 : ps.width) + 255) / 256);
+      for (uint32_t it = 0; it < cnt; it++) b.lists[vp ? L_R16V : L_R16H].push_back({I, it});
+      continue;
+    }
     if (!(di < (int)b.coef_hit.size() && (b.coef_hit[di] >> s) & 1u)) b.lists[L_COEF].push_back({I, (uint32_t)s});
     if (hv && s < 2) continue;  // k_resize_hv runs both
     if (s == 0 && (ps.mode & kHDecode)) continue;  // k_band_dec runs it

@@ -102,6 +102,11 @@ void launch_png_unfilter(hipStream_t st, ImageDesc *imgs, const WgItem *tasks, u
 void launch_png_expand(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // 16-bit images: 256 pixel pairs per workgroup (byte swap, tRNS key, Adam7 scatter)
 void launch_png_expand16(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// 16-bit resize (dg_resize16.hip, option "resize16"): taps = 256 table entries of a pass per workgroup
+// (item0 bit 31 = pass), v = 256 sample quads of an intermediate row, h = 256 output pixels of a row
+void launch_r16_taps(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_r16_v(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_r16_h(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // alpha program at `point` (0 before call 1, 1 between the calls, 2 after call 2): 256 pixels per workgroup
 void launch_alpha(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, int point);
 size_t png_inflate_smem();

@@ -137,8 +137,8 @@ const dg_bucket_table *dg_ctx_buckets(const dg_ctx *ctx);
 
 /* Output metadata, mirrors ImagePayload (structs.rs:52-71).  channels and
  * bit_depth are the decoded image's (pre-transform, image_processing.rs:347-351)
- * unless image_to_rgb8 converted it (then 3 / 8).  bit_depth 16 (option
- * "png16"): the output is native-endian uint16 samples, HWC and tightly packed,
+ * unless image_to_rgb8 converted it (then 3 / 8).  bit_depth 16 (options
+ * "png16", "resize16"): the output is native-endian uint16 samples, HWC and tightly packed,
  * nbytes = 2 * width * height * channels (DynamicImage::into_bytes). */
 typedef struct dg_payload_meta {
   uint32_t original_width, original_height;
@@ -262,8 +262,16 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 image_to_rgb8 every sample is reduced as (v + 128) / 257, luma replicated, alpha
  *                 dropped (meta 3 / 8), and the encoders take the result.  Still DG_ERR_UNSUPPORTED
  *                 (dg_last_error says which): a 16-bit image whose size differs from its bucket's
- *                 (the reference resizes it with image's own f32 Lanczos3), and one that would reach
- *                 an encoder as 16-bit (pre_encode_images without image_to_rgb8)
+ *                 (the reference resizes it with image's own f32 Lanczos3: option "resize16"), and one
+ *                 that would reach an encoder as 16-bit (pre_encode_images without image_to_rgb8)
+ *   "resize16"    1 = with "png16", a 16-bit PNG whose size differs from its bucket's (the closest or a
+ *                 forced one) is resized to it on the GPU (default 0: DG_ERR_UNSUPPORTED).  The
+ *                 resize is the image crate's resize_to_fill(w, h, Lanczos3), as the reference
+ *                 applies it to every non-U8 pixel type: a vertical then a horizontal f32 pass, one
+ *                 rounding at the end, an integer centre crop, no alpha premultiply (a restatement,
+ *                 DESIGN.md "16-bit resize").  meta.width / height are the bucket's, bit_depth 16,
+ *                 nbytes = 2 * width * height * channels; image_to_rgb8 converts the resized samples
+ *                 and the encoders then take them.  16-bit into an encoder stays DG_ERR_UNSUPPORTED
  *   "prog_split"  1 = progressive members of a dg_submit run in the progressive aggregate (default 1,
  *                 see dg_wait_ready); 0 = in the submission's own batch
  *   "prog_batch"  progressive aggregate: launched once it holds this many images (default 2048)
