@@ -8,11 +8,15 @@
 //   k_penc_count   one thread per 1 KiB piece of the filtered stream: greedy
 //                  run-length parse (DEFLATE matches at distance 1), bits of
 //                  the piece under the fixed Huffman code, Adler-32 partials
+//   [option "penc_dynamic": k_penc_count also builds the image's histogram;
+//   k_penc_tree     one workgroup per image: per-image Huffman code, block
+//                   header, dynamic block or fixed (dg_penc_tree.h)
+//   k_penc_count_dyn  piece bit lengths under the image's code ]
 //   k_enc_scan     (dg_enc.hip) exclusive scan of the piece bit lengths
 //   k_penc_write   one thread per piece: the codes OR-ed LSB-first into the
 //                  zeroed bit buffer at the piece's offset
 //   k_penc_final   one workgroup per image: PNG signature + IHDR (host bytes),
-//                  IDAT = zlib(78 01, one fixed-Huffman block, Adler-32),
+//                  IDAT = zlib(78 01, one fixed- or dynamic-Huffman block, Adler-32),
 //                  chunk CRC-32 (parallel slices combined with a GF(2)
 //                  shift operator), IEND
 //
@@ -22,6 +26,7 @@
 // decoded pixels equal the encoder's input bit for bit.
 #include <hip/hip_runtime.h>
 
+#include "dg_penc_tree.h"
 #include "dg_types.h"
 #include "kernels.h"
 
@@ -130,8 +135,9 @@ __device__ __forceinline__ void len_code(uint32_t L, uint32_t &sym, uint32_t &eb
 
 // Greedy parse of [p0, p1): a run of >= 3 bytes equal to the byte before is
 // one match at distance 1 (length 3..258); everything else a literal.
-template <class Emit>
-__device__ __forceinline__ void penc_parse(const DG_GLOBAL uint8_t *s, uint32_t p0, uint32_t p1, Emit emit) {
+// tok(symbol, extra bits, extra value): a literal 0..255 or a length symbol.
+template <class Tok>
+__device__ __forceinline__ void penc_parse(const DG_GLOBAL uint8_t *s, uint32_t p0, uint32_t p1, Tok tok) {
   uint32_t i = p0;
   while (i < p1) {
     if (i > 0) {
@@ -139,54 +145,168 @@ __device__ __forceinline__ void penc_parse(const DG_GLOBAL uint8_t *s, uint32_t 
       uint32_t k = 0;
       while (k < 258 && i + k < p1 && s[i + k] == prev) k++;
       if (k >= 3) {
-        uint32_t sym, eb, ev, code, len;
+        uint32_t sym, eb, ev;
         len_code(k, sym, eb, ev);
-        fixed_code(sym, code, len);
-        emit(code, len);
-        if (eb) emit(ev, eb);
-        emit(0u, 5u);  // distance code 0 (distance 1), 5 bits, no extra
+        tok(sym, eb, ev);
         i += k;
         continue;
       }
     }
-    uint32_t code, len;
-    fixed_code(s[i], code, len);
-    emit(code, len);
+    tok(s[i], 0u, 0u);
     i++;
   }
 }
 
+// A token under the fixed code: a match adds its extra bits and the 5-bit
+// distance code 0 (distance 1, no extra).
+template <class Emit>
+__device__ __forceinline__ void fixed_token(uint32_t sym, uint32_t eb, uint32_t ev, Emit emit) {
+  uint32_t code, len;
+  fixed_code(sym, code, len);
+  emit(code, len);
+  if (sym > 256) {
+    if (eb) emit(ev, eb);
+    emit(0u, 5u);
+  }
+}
+
+// ... under the image's own code (table word: bit-reversed code | length << 16):
+// the one distance code is the single bit 0, sent with the extra bits.
+template <class Emit>
+__device__ __forceinline__ void table_token(const uint32_t *tab, uint32_t sym, uint32_t eb, uint32_t ev, Emit emit) {
+  const uint32_t t = tab[sym];
+  emit(t & 0xFFFFu, t >> 16);
+  if (sym > 256) emit(ev, eb + 1u);
+}
+
+static_assert(kPencTabBytes >= kPtTableWords * 4, "the histogram / code table region");
+
+// HIST (option "penc_dynamic", images with e.tab): the workgroup also counts
+// its tokens by symbol in LDS and adds the counts to the image's histogram.
+template <bool HIST>
 __global__ __launch_bounds__(256) void k_penc_count(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  __shared__ uint32_t hist[HIST ? kPtTableWords : 1];
   const WgItem it = list[blockIdx.x];
   const ImageDesc &im = imgs[it.image];
   if (im.status) return;
   const EncDesc &e = im.enc;
   const uint32_t pc = it.item0 + threadIdx.x;
-  if (pc >= e.nblocks) return;
-  const uint32_t N = e.h * (e.w * e.C + 1);
-  const uint32_t p0 = pc * kPencPiece, p1 = min(p0 + kPencPiece, N);
-  const DG_GLOBAL uint8_t *s = gp<const uint8_t>(e.coef);
-  uint32_t bits = 0;
-  penc_parse(s, p0, p1, [&](uint32_t, uint32_t n) { bits += n; });
-  gp<uint32_t>(e.bits)[pc] = bits;
-  // Adler-32 partials: S = sum of bytes, T = sum (L - j) * byte_j, both mod 65521
-  uint64_t S = 0, T = 0;
-  const uint32_t L = p1 - p0;
-  for (uint32_t j = 0; j < L; j++) {
-    const uint32_t v = s[p0 + j];
-    S += v;
-    T += (uint64_t)(L - j) * v;
+  const bool count = HIST && e.tab;  // (uniform: a workgroup belongs to one image)
+  if (HIST) {
+    for (uint32_t i = threadIdx.x; i < kPtTableWords; i += 256) hist[i] = 0;
+    __syncthreads();
   }
-  DG_GLOBAL uint32_t *adl = gp<uint32_t>(e.aux) + 2 * (size_t)pc;
-  adl[0] = (uint32_t)(S % kAdlerMod);
-  adl[1] = (uint32_t)(T % kAdlerMod);
+  if (pc < e.nblocks) {
+    const uint32_t N = e.h * (e.w * e.C + 1);
+    const uint32_t p0 = pc * kPencPiece, p1 = min(p0 + kPencPiece, N);
+    const DG_GLOBAL uint8_t *s = gp<const uint8_t>(e.coef);
+    uint32_t bits = 0;
+    penc_parse(s, p0, p1, [&](uint32_t sym, uint32_t eb, uint32_t ev) {
+      fixed_token(sym, eb, ev, [&](uint32_t, uint32_t n) { bits += n; });
+      if (HIST && count) atomicAdd(&hist[sym], 1u);
+    });
+    gp<uint32_t>(e.bits)[pc] = bits;
+    // Adler-32 partials: S = sum of bytes, T = sum (L - j) * byte_j, both mod 65521
+    uint64_t S = 0, T = 0;
+    const uint32_t L = p1 - p0;
+    for (uint32_t j = 0; j < L; j++) {
+      const uint32_t v = s[p0 + j];
+      S += v;
+      T += (uint64_t)(L - j) * v;
+    }
+    DG_GLOBAL uint32_t *adl = gp<uint32_t>(e.aux) + 2 * (size_t)pc;
+    adl[0] = (uint32_t)(S % kAdlerMod);
+    adl[1] = (uint32_t)(T % kAdlerMod);
+  }
+  if (HIST) {
+    __syncthreads();
+    if (count) {
+      DG_GLOBAL uint32_t *gh = gp<uint32_t>(e.tab);
+      for (uint32_t i = threadIdx.x; i < kPtLit; i += 256)
+        if (hist[i]) atomicAdd((uint32_t *)&gh[i], hist[i]);
+    }
+  }
 }
 
-__global__ __launch_bounds__(256) void k_penc_write(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+// One workgroup per image: code lengths, codes, the block header and the
+// choice between the dynamic and the fixed block (dg_penc_tree.h), the merges
+// of the package-merge lists shared by rank among the 256 threads.  Decide
+// first, write second: the header (up to ~512 bytes) goes into the bit buffer
+// only when the dynamic block was chosen, which is then shorter than the
+// fixed block the buffer is sized for; a fixed image's buffer, table words
+// and descriptor stay as the host left them.
+struct TreeSmem {
+  PtWork work;
+  PtOut out;
+  uint32_t f[kPtTableWords];
+  uint8_t seq[kPtTableWords];
+};
+
+__global__ __launch_bounds__(256) void k_penc_tree(ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  __shared__ TreeSmem sm;
+  const WgItem it = list[blockIdx.x];
+  ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  EncDesc &e = im.enc;
+  if (!e.tab) return;
+  const uint32_t t = threadIdx.x;
+  DG_GLOBAL uint32_t *tab = gp<uint32_t>(e.tab);
+  for (uint32_t i = t; i < kPtTableWords; i += 256) sm.f[i] = i < kPtLit ? tab[i] : 0u;
+  __syncthreads();
+  if (t == 0) sm.f[256] = 1;  // the end-of-block
+  __syncthreads();
+  pt_build(sm.f, sm.out, sm.work, sm.seq, t, 256u, [] { __syncthreads(); });
+  if (!sm.out.dyn) return;
+  for (uint32_t i = t; i < kPtTableWords; i += 256) tab[i] = sm.out.table[i];
+  DG_GLOBAL uint32_t *w = gp<uint32_t>(e.words);
+  const uint32_t nw = (sm.out.hdr_bits + 31) / 32;  // <= kPtHdrWords; the zeroed words past the header's last stay zero
+  for (uint32_t i = t; i < nw; i += 256) w[i] = sm.out.hdr[i];
+  if (t == 0) {
+    e.dyn = 1;
+    e.hdr_bits = sm.out.hdr_bits;
+    e.eob_len = (uint16_t)sm.out.litlen[256];
+  }
+}
+
+// Second pass over the pieces of the images that took the dynamic block:
+// their bit lengths under the image's table (k_enc_scan turns them into offsets).
+__global__ __launch_bounds__(256) void k_penc_count_dyn(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  __shared__ uint32_t tab[kPtTableWords];
   const WgItem it = list[blockIdx.x];
   const ImageDesc &im = imgs[it.image];
   if (im.status) return;
   const EncDesc &e = im.enc;
+  if (!e.dyn) return;
+  const DG_GLOBAL uint32_t *gt = gp<const uint32_t>(e.tab);
+  for (uint32_t i = threadIdx.x; i < kPtTableWords; i += 256) tab[i] = gt[i];
+  __syncthreads();
+  const uint32_t pc = it.item0 + threadIdx.x;
+  if (pc >= e.nblocks) return;
+  const uint32_t N = e.h * (e.w * e.C + 1);
+  const uint32_t p0 = pc * kPencPiece, p1 = min(p0 + kPencPiece, N);
+  uint32_t bits = 0;
+  penc_parse(gp<const uint8_t>(e.coef), p0, p1, [&](uint32_t sym, uint32_t eb, uint32_t ev) {
+    table_token(tab, sym, eb, ev, [&](uint32_t, uint32_t n) { bits += n; });
+  });
+  gp<uint32_t>(e.bits)[pc] = bits;
+}
+
+// DYN (option "penc_dynamic"): an image that took the dynamic block packs its
+// tokens under its table (in LDS), from bit hdr_bits on, and its last piece
+// appends the end-of-block code (the fixed one is seven zero bits: nothing to write).
+template <bool DYN>
+__global__ __launch_bounds__(256) void k_penc_write(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  __shared__ uint32_t tab[DYN ? kPtTableWords : 1];
+  const WgItem it = list[blockIdx.x];
+  const ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  const EncDesc &e = im.enc;
+  const bool dyn = DYN && e.dyn;  // (uniform: a workgroup belongs to one image)
+  if (DYN && dyn) {
+    const DG_GLOBAL uint32_t *gt = gp<const uint32_t>(e.tab);
+    for (uint32_t i = threadIdx.x; i < kPtTableWords; i += 256) tab[i] = gt[i];
+    __syncthreads();
+  }
   const uint32_t pc = it.item0 + threadIdx.x;
   if (pc >= e.nblocks) return;
   const uint32_t N = e.h * (e.w * e.C + 1);
@@ -194,7 +314,7 @@ __global__ __launch_bounds__(256) void k_penc_write(const ImageDesc *__restrict_
   const DG_GLOBAL uint8_t *s = gp<const uint8_t>(e.coef);
   DG_GLOBAL uint32_t *w = gp<uint32_t>(e.words);
   // stream bit k = bit (k & 31) of word k >> 5 (little-endian words = the byte stream)
-  uint32_t pos = 3u + gp<const uint32_t>(e.bits)[pc];  // after the 3-bit block header
+  uint32_t pos = (dyn ? e.hdr_bits : 3u) + gp<const uint32_t>(e.bits)[pc];  // after the block header
   uint64_t acc = 0;
   uint32_t nacc = pos & 31u, wi = pos >> 5;
   auto emit = [&](uint32_t v, uint32_t n) {
@@ -207,9 +327,14 @@ __global__ __launch_bounds__(256) void k_penc_write(const ImageDesc *__restrict_
       wi++;
     }
   };
-  penc_parse(s, p0, p1, emit);
+  if (DYN && dyn) {
+    penc_parse(s, p0, p1, [&](uint32_t sym, uint32_t eb, uint32_t ev) { table_token(tab, sym, eb, ev, emit); });
+    if (pc + 1 == e.nblocks) emit(tab[256] & 0xFFFFu, tab[256] >> 16);
+  } else {
+    penc_parse(s, p0, p1, [&](uint32_t sym, uint32_t eb, uint32_t ev) { fixed_token(sym, eb, ev, emit); });
+  }
   if (nacc) atomicOr((uint32_t *)&w[wi], (uint32_t)acc);
-  if (pc == 0) atomicOr((uint32_t *)&w[0], 3u);  // BFINAL = 1, BTYPE = 01 (fixed Huffman)
+  if (pc == 0 && !dyn) atomicOr((uint32_t *)&w[0], 3u);  // BFINAL = 1, BTYPE = 01 (fixed Huffman)
 }
 
 // ------------------------------------------------------------ container
@@ -271,7 +396,7 @@ __global__ __launch_bounds__(1024) void k_penc_final(ImageDesc *__restrict__ img
   EncDesc &e = im.enc;
   const uint32_t t = threadIdx.x;
   const uint32_t N = e.h * (e.w * e.C + 1);
-  const uint32_t dbits = 3u + e.total_bits + 7u;  // header, pieces, end-of-block (7 zero bits)
+  const uint32_t dbits = e.hdr_bits + e.total_bits + e.eob_len;  // header (3 bits fixed), pieces, end-of-block (7 zero bits fixed)
   const uint32_t dbytes = (dbits + 7) / 8;
   const uint32_t zlen = 2 + dbytes + 4;
   DG_GLOBAL uint8_t *out = gp<uint8_t>(e.out);
@@ -338,11 +463,25 @@ __global__ __launch_bounds__(1024) void k_penc_final(ImageDesc *__restrict__ img
 void launch_penc_filter(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   if (nwg) hipLaunchKernelGGL(k_penc_filter, dim3(nwg), dim3(256), 0, st, imgs, list);
 }
-void launch_penc_count(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
-  if (nwg) hipLaunchKernelGGL(k_penc_count, dim3(nwg), dim3(256), 0, st, imgs, list);
+void launch_penc_count(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic) {
+  if (!nwg) return;
+  if (dynamic)
+    hipLaunchKernelGGL(k_penc_count<true>, dim3(nwg), dim3(256), 0, st, imgs, list);
+  else
+    hipLaunchKernelGGL(k_penc_count<false>, dim3(nwg), dim3(256), 0, st, imgs, list);
 }
-void launch_penc_write(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
-  if (nwg) hipLaunchKernelGGL(k_penc_write, dim3(nwg), dim3(256), 0, st, imgs, list);
+void launch_penc_tree(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_penc_tree, dim3(nwg), dim3(256), 0, st, imgs, list);
+}
+void launch_penc_count_dyn(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_penc_count_dyn, dim3(nwg), dim3(256), 0, st, imgs, list);
+}
+void launch_penc_write(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic) {
+  if (!nwg) return;
+  if (dynamic)
+    hipLaunchKernelGGL(k_penc_write<true>, dim3(nwg), dim3(256), 0, st, imgs, list);
+  else
+    hipLaunchKernelGGL(k_penc_write<false>, dim3(nwg), dim3(256), 0, st, imgs, list);
 }
 void launch_penc_final(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   if (nwg) hipLaunchKernelGGL(k_penc_final, dim3(nwg), dim3(1024), 0, st, imgs, list);

@@ -247,6 +247,7 @@ struct EncTables {
   uint16_t code[4][256];  // DC luma, AC luma, DC chroma, AC chroma
   uint8_t len[4][256];
 };
+constexpr uint32_t kPencTabBytes = 1280;  // png, option "penc_dynamic": 288 words of histogram / code table, padded to 256
 struct EncDesc {
   uint64_t src;        // the transformed image (C channels, row stride src_stride)
   uint64_t coef;       // int16 [nblocks][64], quantised, zigzag order, MCU-interleaved blocks
@@ -254,12 +255,15 @@ struct EncDesc {
   uint64_t words;      // scan bit buffer (stream bytes in memory order), zeroed per batch
   uint64_t out;        // header | stuffed scan | EOI
   uint64_t hdr;        // header bytes (SOI .. SOS)
-  uint64_t tab;        // EncTables
+  uint64_t tab;        // EncTables; png: 0, or with option "penc_dynamic" the image's 288 words that hold the
+                       // literal/length histogram (zeroed per batch) and then, for a dynamic block, its code table
   uint32_t src_stride, C, ncomp, mode;  // mode 1: resized LA image read as luma bytes
   uint32_t w, h, nbx, nby;
   uint32_t nblocks, hdr_len, total_bits, enc_bytes;
-  uint32_t active, png, pad[2];  // png: PNG re-encode (dg_penc.hip): coef = filtered stream,
-                                 // nblocks = 1 KiB pieces, bits = piece bit lengths
+  uint32_t active, png;  // png: PNG re-encode (dg_penc.hip): coef = filtered stream,
+                         // nblocks = 1 KiB pieces, bits = piece bit lengths
+  uint32_t hdr_bits;     // png: bits in front of the first token: 3, or the dynamic block's header (k_penc_tree)
+  uint16_t dyn, eob_len; // png: 1 = dynamic block (k_penc_tree chose it); bits of the end-of-block code (7 fixed)
   uint64_t aux;                  // png: Adler-32 partials per piece (uint32 x 2)
   uint8_t q[2][64];    // quantisation tables, natural order
 };

@@ -404,6 +404,16 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     resize16_ = v != 0;
     return DG_OK;
   }
+  if (k == "penc_dynamic") {
+    // PNG re-encode (pre_encode_images, encode_format png): 1 = an image whose
+    // DEFLATE block is strictly shorter under a Huffman code built from its own
+    // histogram takes a dynamic block (dg_penc_tree.h); every other image, and
+    // every image with 0 (the default), takes the fixed block byte for byte as
+    // before.  Nothing changes for JPEG re-encoding.
+    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
+    penc_dynamic_ = v != 0;
+    return DG_OK;
+  }
   if (k == "prog_lanes") {  // dg_decode_one: progressive batches in flight on the progressive slots; 0: mixed in
     if (v < 0 || v > kProgSlots) return opt_error(k, v, "valid unless v < 0 || v > " + std::to_string(kProgSlots));
     prog_lanes_ = (int)v;
@@ -1826,10 +1836,14 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     launch_enc_fdct(sl.st, dd, lst(L_ENC_MCU), cnt(L_ENC_MCU));
     launch_enc_count(sl.st, dd, lst(L_ENC_BLK), cnt(L_ENC_BLK));
     launch_penc_filter(sl.st, dd, lst(L_PENC_ROW), cnt(L_PENC_ROW));
-    launch_penc_count(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE));
+    launch_penc_count(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE), b.penc_dyn);
+    if (b.penc_dyn) {  // per-image codes and the block choice, then the chosen images' pieces under their codes
+      launch_penc_tree(sl.st, dm, lst(L_PENC_IMG), cnt(L_PENC_IMG));
+      launch_penc_count_dyn(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE));
+    }
     launch_enc_scan(sl.st, dm, lst(L_ENC_IMG), cnt(L_ENC_IMG));
     launch_enc_write(sl.st, dd, lst(L_ENC_BLK), cnt(L_ENC_BLK));
-    launch_penc_write(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE));
+    launch_penc_write(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE), b.penc_dyn);
     launch_enc_stuff(sl.st, dm, lst(L_ENC_IMG), cnt(L_ENC_IMG));
     launch_penc_final(sl.st, dm, lst(L_PENC_IMG), cnt(L_PENC_IMG));
   }

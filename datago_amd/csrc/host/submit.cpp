@@ -135,6 +135,7 @@ struct Offs {
   size_t final_off, tmp, out, ds, mk, chunk, stage;
   size_t zs, raw, unf, pal;
   size_t tout, ecoef, ebits, ewords, hdr, eaux;  // JPEG / PNG re-encode
+  size_t etab;  // PNG, option "penc_dynamic": bytes of histogram / code table at the head of ewords
   // alpha programs: buffer = dst of pass `stage` (-1: the decoded image), byte offset
   int aop_stage[kAlphaPoints];
   size_t aop_off[kAlphaPoints];
@@ -906,6 +907,14 @@ void Context::layout_output_and_encode(const SubmitArgs &a, int i, int last_stag
     o.ebits = bl.L.take((size_t)e.nblocks * 4, 256);
     o.eaux = bl.L.take((size_t)e.nblocks * 8, 256);
     o.ewords = (size_t)((3 + 9 * nf + 7 + 64) / 8 + 64) / 4 * 4;  // size for now; placed with the batch's regions
+    e.hdr_bits = 3;  // the fixed block, unless k_penc_tree chooses the dynamic one (never longer: same buffer)
+    e.eob_len = 7;
+    e.dyn = 0;
+    // option "penc_dynamic": the image's histogram / code table (dg_penc_tree.h) in front of its bit buffer,
+    // inside the region the batch zeroes
+    o.etab = penc_dynamic_ ? kPencTabBytes : 0;
+    o.ewords += o.etab;
+    b.penc_dyn = b.penc_dyn || penc_dynamic_;
     b.any_enc = true;
   } else if (p.encode) {  // the transform lands in tout; the JPEG goes to the caller's buffer
     EncDesc &e = d.enc;
@@ -1088,7 +1097,8 @@ void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const Bat
       e.out = user_out;
       e.coef = (uint64_t)(uintptr_t)(S + o.ecoef);
       e.bits = (uint64_t)(uintptr_t)(S + o.ebits);
-      e.words = (uint64_t)(uintptr_t)(S + o.ewords);
+      e.words = (uint64_t)(uintptr_t)(S + o.ewords + o.etab);
+      if (e.png) e.tab = o.etab ? (uint64_t)(uintptr_t)(S + o.ewords) : 0;
       e.aux = o.eaux ? (uint64_t)(uintptr_t)(S + o.eaux) : 0;
       e.hdr = o.hdr + 1;  // blob offset + 1: made absolute with the meta buffer
     }
@@ -1427,7 +1437,7 @@ dg_status Context::stage_and_upload(const SubmitArgs &a, Slot &sl, Batch &b, con
     if (d.fmt == kFmtPng && d.png.pal) d.png.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.png.pal - 1);
     if (d.enc.active) {
       d.enc.hdr = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.enc.hdr - 1);
-      d.enc.tab = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + b.enctab_off);
+      if (!d.enc.png) d.enc.tab = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + b.enctab_off);
     }
   }
   size_t stage_bytes = b.meta_bytes + (a.host_io ? bl.IN.off : 0);

@@ -272,6 +272,11 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 DESIGN.md "16-bit resize").  meta.width / height are the bucket's, bit_depth 16,
  *                 nbytes = 2 * width * height * channels; image_to_rgb8 converts the resized samples
  *                 and the encoders then take them.  16-bit into an encoder stays DG_ERR_UNSUPPORTED
+ *   "penc_dynamic" 1 = PNG re-encode (pre_encode_images with encode_format png): an image whose DEFLATE
+ *                 block is strictly shorter under a Huffman code built from its own histogram takes a
+ *                 dynamic block (RFC 1951 3.2.7; DESIGN.md "PNG re-encode" states the bytes); every other
+ *                 image keeps the fixed block.  Default 0: the fixed block always, byte for byte as
+ *                 before.  The bound dg_output_size reports is the same; JPEG re-encoding ignores it
  *   "prog_split"  1 = progressive members of a dg_submit run in the progressive aggregate (default 1,
  *                 see dg_wait_ready); 0 = in the submission's own batch
  *   "prog_batch"  progressive aggregate: launched once it holds this many images (default 2048)
