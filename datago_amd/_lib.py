@@ -276,8 +276,11 @@ def meta_status(metas) -> np.ndarray:
 def payload_array(buf: np.ndarray, m: PayloadMeta) -> np.ndarray:
     """The HWC pixels of a decoded payload over the bytes of `buf` (a uint8
     output buffer), without a copy: uint16 samples in native byte order when
-    meta.bit_depth == 16 (context option "png16"), uint8 otherwise."""
+    meta.bit_depth == 16 (context option "png16"), uint8 otherwise.  An
+    encoded payload (pre_encode_images) is its file's bytes, flat."""
     a = buf[: m.nbytes]
+    if m.is_encoded:
+        return a
     sb = 2 if m.bit_depth == 16 else 1
     if sb == 2:
         a = a.view(np.uint16)
@@ -326,7 +329,7 @@ class Context:
                  downsampling_ratio: int = 0, min_aspect_ratio: float = 0.0, max_aspect_ratio: float = 0.0,
                  image_to_rgb8: bool = False, pre_encode_images: bool = False, encode_format: int = 0,
                  jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False,
-                 resize16: bool = False, penc_dynamic: bool = False):
+                 resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -345,6 +348,8 @@ class Context:
             self.set_option("png16", 1)
         if resize16:  # ... and those that are not their bucket's size resize to it (with png16)
             self.set_option("resize16", 1)
+        if penc16:  # ... and re-encode as bit-depth-16 PNGs under pre_encode_images with encode_format png
+            self.set_option("penc16", 1)
         if penc_dynamic:  # PNG re-encode: per-image Huffman codes where they make the file shorter
             self.set_option("penc_dynamic", 1)
 

@@ -5,6 +5,10 @@
 //   k_penc_filter  one wave per row: the five PNG filters (spec 9.2), the one
 //                  with the smallest sum of |byte as i8| is kept (adaptive
 //                  heuristic, PNG spec 12.8), filtered row -> the stream
+//   [option "penc16": k_penc_filter16 does the same for an image of uint16
+//                  samples: every sample high byte first, bpp = 2 x samples
+//                  per pixel (dg_penc16.h); everything after the filter takes
+//                  the stream as bytes, EncDesc::C being bytes per pixel ]
 //   k_penc_count   one thread per 1 KiB piece of the filtered stream: greedy
 //                  run-length parse (DEFLATE matches at distance 1), bits of
 //                  the piece under the fixed Huffman code, Adler-32 partials
@@ -26,6 +30,7 @@
 // decoded pixels equal the encoder's input bit for bit.
 #include <hip/hip_runtime.h>
 
+#include "dg_penc16.h"
 #include "dg_penc_tree.h"
 #include "dg_types.h"
 #include "kernels.h"
@@ -84,6 +89,43 @@ __global__ __launch_bounds__(256) void k_penc_filter(const ImageDesc *__restrict
     const uint32_t v = cur[x], a = x >= bpp ? cur[x - bpp] : 0u, b = up ? up[x] : 0u,
                    c = (up && x >= bpp) ? up[x - bpp] : 0u;
     dst[1 + x] = (uint8_t)filt_byte(best, v, a, b, c);
+  }
+}
+
+// 16-bit samples (option "penc16"): one wave per row, a lane takes quads of
+// four row bytes = two samples (dg_penc16.h).  The samples come in as dwords
+// where the row's address allows and as 2-byte loads otherwise (rows are
+// tightly packed: a row of an odd number of samples shifts the next by 2),
+// never as bytes; v_perm_b32 turns them high byte first.  e.C is bytes per
+// pixel here (2, 4, 6 or 8), src_stride = w * C.
+__global__ __launch_bounds__(256) void k_penc_filter16(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  const WgItem it = list[blockIdx.x];
+  const ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  const EncDesc &e = im.enc;
+  const uint32_t y = it.item0 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (y >= e.h) return;
+  const uint32_t hs = e.C >> 1, n = e.w * hs, rb = 2 * n;  // samples per pixel, per row; row bytes
+  const uint64_t ca = e.src + (uint64_t)y * e.src_stride, ua = ca - e.src_stride;
+  const DG_GLOBAL uint16_t *cur = gp<const uint16_t>(ca), *up = y ? gp<const uint16_t>(ua) : nullptr;
+  const bool cal = (ca & 3u) == 0, ual = (ua & 3u) == 0;
+  uint32_t sum[5] = {0, 0, 0, 0, 0};
+  for (uint32_t x = 4 * lane; x < rb; x += 256) p16_sums(p16_quad(cur, up, x, n, hs, cal, ual), min(4u, rb - x), sum);
+#pragma unroll
+  for (uint32_t f = 0; f < 5; f++)
+    for (int o = 32; o > 0; o >>= 1) sum[f] += __shfl_xor(sum[f], o, 64);
+  const uint32_t best = p16_best(sum);
+  DG_GLOBAL uint8_t *dst = gp<uint8_t>(e.coef) + (size_t)y * (rb + 1);
+  if (lane == 0) dst[0] = (uint8_t)best;
+  for (uint32_t x = 4 * lane; x < rb; x += 256) {
+    const uint32_t r = p16_apply(best, p16_quad(cur, up, x, n, hs, cal, ual));
+    DG_GLOBAL uint8_t *q = dst + 1 + x;  // (any alignment: rows of the stream are rb + 1 bytes)
+    q[0] = (uint8_t)r;
+    q[1] = (uint8_t)(r >> 8);
+    if (x + 2 < rb) {  // rb is even: a quad holds 4 or 2 row bytes
+      q[2] = (uint8_t)(r >> 16);
+      q[3] = (uint8_t)(r >> 24);
+    }
   }
 }
 
@@ -462,6 +504,9 @@ __global__ __launch_bounds__(1024) void k_penc_final(ImageDesc *__restrict__ img
 
 void launch_penc_filter(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   if (nwg) hipLaunchKernelGGL(k_penc_filter, dim3(nwg), dim3(256), 0, st, imgs, list);
+}
+void launch_penc_filter16(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_penc_filter16, dim3(nwg), dim3(256), 0, st, imgs, list);
 }
 void launch_penc_count(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic) {
   if (!nwg) return;

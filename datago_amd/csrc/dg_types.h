@@ -257,7 +257,8 @@ struct EncDesc {
   uint64_t hdr;        // header bytes (SOI .. SOS)
   uint64_t tab;        // EncTables; png: 0, or with option "penc_dynamic" the image's 288 words that hold the
                        // literal/length histogram (zeroed per batch) and then, for a dynamic block, its code table
-  uint32_t src_stride, C, ncomp, mode;  // mode 1: resized LA image read as luma bytes
+  uint32_t src_stride, C, ncomp, mode;  // C: bytes per pixel (channels; png of 16-bit samples, option "penc16":
+                                        // 2 x channels); mode 1: resized LA image read as luma bytes
   uint32_t w, h, nbx, nby;
   uint32_t nblocks, hdr_len, total_bits, enc_bytes;
   uint32_t active, png;  // png: PNG re-encode (dg_penc.hip): coef = filtered stream,

@@ -389,7 +389,8 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     // 16-bit PNGs on the GPU (default off: DG_ERR_UNSUPPORTED, the caller's CPU
     // decoder takes them).  1: they decode to native-endian u16 samples
     // (bit_depth 16), or to RGB8 under image_to_rgb8; a 16-bit image that would
-    // need the resize or an encoder stays DG_ERR_UNSUPPORTED.
+    // need the resize or an encoder stays DG_ERR_UNSUPPORTED unless "resize16" /
+    // "penc16" take it.
     if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
     png16_ = v != 0;
     return DG_OK;
@@ -399,9 +400,21 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     // DG_ERR_UNSUPPORTED).  1, together with "png16": they resize with the
     // image crate's resize_to_fill(Lanczos3), which the reference uses for
     // every non-U8 pixel type (dg_resize16.h); 16-bit into an encoder stays
-    // DG_ERR_UNSUPPORTED.
+    // DG_ERR_UNSUPPORTED unless "penc16" is on.
     if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
     resize16_ = v != 0;
+    return DG_OK;
+  }
+  if (k == "penc16") {
+    // 16-bit PNGs into the PNG re-encoder (default off: DG_ERR_UNSUPPORTED).  1,
+    // together with "png16" (and "resize16" for an image that is not its
+    // bucket's size): under pre_encode_images with encode_format png the
+    // transformed samples come back as a bit-depth-16 PNG, as the reference's
+    // PngEncoder writes an ImageLuma16 / LumaA16 / Rgb16 / Rgba16
+    // (k_penc_filter16, dg_penc16.h).  The JPEG encoder takes 8-bit samples
+    // only.  8-bit images and image_to_rgb8 contexts are untouched.
+    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
+    penc16_ = v != 0;
     return DG_OK;
   }
   if (k == "penc_dynamic") {
@@ -1447,17 +1460,25 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
       return DG_OK;
     }
   }
-  if (deep && cfg_.pre_encode_images && !cfg_.image_to_rgb8) {
+  const bool deep_enc = deep && cfg_.pre_encode_images && !cfg_.image_to_rgb8;  // 16-bit samples at an encoder
+  if (deep_enc && !penc16_) {
     p.png.why = "PNG: 16-bit image to an encoder (the GPU encoders take 8-bit samples)";
+    p.status = DG_ERR_UNSUPPORTED;
+    return DG_OK;
+  }
+  if (deep_enc && cfg_.encode_format != 0) {  // image 0.25's JpegEncoder rejects 16-bit colour types: the reference drops the sample
+    p.png.why = "PNG: 16-bit image to the JPEG encoder (it takes 8-bit samples only; option \"penc16\" covers encode_format png)";
     p.status = DG_ERR_UNSUPPORTED;
     return DG_OK;
   }
   if (cfg_.pre_encode_images) {  // image_processing.rs:374-419
     p.encode = true;
     p.enc_png = cfg_.encode_format == 0;
-    // a resized LA image is a GrayImage over its LA bytes by now (image_to_dyn_image)
-    p.enc_la_gray = p.out_c == 2 && has_cfg_ && !(W == p.out_w && H == p.out_h);
-    p.out_bytes = p.enc_png ? png_enc_bound(ow, oh, p.enc_la_gray ? 1 : p.out_c) : jpeg_enc_bound(ow, oh, p.out_c);
+    // a resized LA image is a GrayImage over its LA bytes by now (image_to_dyn_image);
+    // a resized LA16 image went through resize_to_fill instead and is still LumaA16
+    p.enc_la_gray = !deep_enc && p.out_c == 2 && has_cfg_ && !(W == p.out_w && H == p.out_h);
+    p.out_bytes = p.enc_png ? png_enc_bound(ow, oh, p.enc_la_gray ? 1 : p.out_c, deep_enc ? 2 : 1)
+                            : jpeg_enc_bound(ow, oh, p.out_c);
     p.channels = -1;  // :416
     // the encoders count bits in 32-bit offsets (~400 MB of output): larger
     // images stay on the caller's CPU encoder
@@ -1836,6 +1857,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     launch_enc_fdct(sl.st, dd, lst(L_ENC_MCU), cnt(L_ENC_MCU));
     launch_enc_count(sl.st, dd, lst(L_ENC_BLK), cnt(L_ENC_BLK));
     launch_penc_filter(sl.st, dd, lst(L_PENC_ROW), cnt(L_PENC_ROW));
+    launch_penc_filter16(sl.st, dd, lst(L_PENC_ROW16), cnt(L_PENC_ROW16));
     launch_penc_count(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE), b.penc_dyn);
     if (b.penc_dyn) {  // per-image codes and the block choice, then the chosen images' pieces under their codes
       launch_penc_tree(sl.st, dm, lst(L_PENC_IMG), cnt(L_PENC_IMG));

@@ -187,6 +187,7 @@ enum ListId {
   L_RVT1, L_RVT3,                                           // V passes on column tiles (k_resize_vt)
   L_EXPAND16,                                               // 16-bit PNG sample step (k_png_expand16)
   L_R16T, L_R16V, L_R16H,                                   // 16-bit resize: tap tables, V pass, H pass (dg_resize16.hip)
+  L_PENC_ROW16,                                             // PNG re-encode of 16-bit samples: filter rows (k_penc_filter16)
   L_COUNT
 };
 static_assert((int)L_COUNT <= 48, "Batch::lists");
@@ -524,6 +525,7 @@ class Context {
   bool progressive_ = true;             // option "progressive"
   bool png16_ = false;                  // option "png16": 16-bit PNGs decode on the GPU
   bool resize16_ = false;               // option "resize16": ... and resize to their bucket (dg_resize16.hip)
+  bool penc16_ = false;                 // option "penc16": ... and go into the PNG re-encoder as 16-bit samples (dg_penc16.h)
   bool penc_dynamic_ = false;           // option "penc_dynamic": PNG re-encode with per-image Huffman codes where shorter
   bool prog_serial_ = false;            // option "prog_serial": serial reader for every scan (A/B)
   bool prog_pipe_ = true;               // option "prog_pipe": all scans in one pipelined launch (0: one launch per level)

@@ -122,7 +122,7 @@ static uint32_t crc32_bytes(const uint8_t *p, size_t n) {
   return ~c;
 }
 
-std::vector<uint8_t> png_enc_header(uint32_t w, uint32_t h, uint32_t C) {
+std::vector<uint8_t> png_enc_header(uint32_t w, uint32_t h, uint32_t C, uint32_t sample_bytes) {
   static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
   std::vector<uint8_t> o(sig, sig + 8);
   auto be32 = [&](uint32_t v) {
@@ -133,7 +133,7 @@ std::vector<uint8_t> png_enc_header(uint32_t w, uint32_t h, uint32_t C) {
   for (char c : {'I', 'H', 'D', 'R'}) o.push_back((uint8_t)c);
   be32(w);
   be32(h);
-  o.push_back(8);                                                // bit depth
+  o.push_back((uint8_t)(8 * sample_bytes));                      // bit depth
   o.push_back((uint8_t)(C == 1 ? 0 : C == 2 ? 4 : C == 3 ? 2 : 6));  // colour type
   o.push_back(0);                                                // deflate
   o.push_back(0);                                                // adaptive filtering
@@ -142,8 +142,8 @@ std::vector<uint8_t> png_enc_header(uint32_t w, uint32_t h, uint32_t C) {
   return o;
 }
 
-uint64_t png_enc_bound(uint32_t w, uint32_t h, uint32_t C) {
-  const uint64_t n = (uint64_t)h * ((uint64_t)w * C + 1);  // filtered stream
+uint64_t png_enc_bound(uint32_t w, uint32_t h, uint32_t C, uint32_t sample_bytes) {
+  const uint64_t n = (uint64_t)h * ((uint64_t)w * C * sample_bytes + 1);  // filtered stream
   return 33 + 8 + 2 + (3 + 9 * n + 7 + 7) / 8 + 4 + 4 + 12 + 16;
 }
 

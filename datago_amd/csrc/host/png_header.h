@@ -36,10 +36,11 @@ struct PngHeader {
 };
 
 bool is_png(const uint8_t *d, size_t n);
-// PNG re-encode (dg_penc.hip): signature + IHDR chunk (8-bit, C = 1/2/3/4
-// channels -> colour type 0/4/2/6, no interlace) and the output size bound.
-std::vector<uint8_t> png_enc_header(uint32_t w, uint32_t h, uint32_t C);
-uint64_t png_enc_bound(uint32_t w, uint32_t h, uint32_t C);
+// PNG re-encode (dg_penc.hip): signature + IHDR chunk (C = 1/2/3/4 channels
+// -> colour type 0/4/2/6, no interlace; sample_bytes 1 / 2 -> bit depth 8 / 16,
+// option "penc16") and the output size bound.
+std::vector<uint8_t> png_enc_header(uint32_t w, uint32_t h, uint32_t C, uint32_t sample_bytes = 1);
+uint64_t png_enc_bound(uint32_t w, uint32_t h, uint32_t C, uint32_t sample_bytes = 1);
 // Walks every chunk header (reads 8 bytes per chunk plus IHDR/PLTE/tRNS payloads).
 // allow16: depth-16 files get their geometry (bpp 2/4/6/8, rowbytes, rawlen,
 // unflen) and PH_OK instead of PH_UNSUPPORTED; out_c then counts 16-bit

@@ -894,11 +894,15 @@ void Context::layout_output_and_encode(const SubmitArgs &a, int i, int last_stag
     e.png = 1;
     e.w = p.out_w;
     e.h = p.out_h;
-    e.C = p.enc_la_gray ? 1 : p.out_c;
+    // 16-bit samples (option "penc16"): C is bytes per pixel, the filter rows go to k_penc_filter16, and the
+    // transform's three endings (k_copy mode 5, the pure-crop window, the horizontal resize pass) write tout
+    // with the tight stride out_w * out_c * 2
+    const uint32_t sb = p.bit_depth == 16 ? 2 : 1;
+    e.C = (p.enc_la_gray ? 1 : p.out_c) * sb;
     e.src_stride = p.enc_la_gray ? p.out_w : d.out_stride;
     const uint64_t nf = (uint64_t)e.h * ((uint64_t)e.w * e.C + 1);
     e.nblocks = (uint32_t)((nf + 1023) / 1024);
-    const std::vector<uint8_t> hdr = png_enc_header(e.w, e.h, e.C);
+    const std::vector<uint8_t> hdr = png_enc_header(e.w, e.h, e.C / sb, sb);
     e.hdr_len = (uint32_t)hdr.size();
     o.hdr = b.blob.size();
     b.blob.insert(b.blob.end(), hdr.begin(), hdr.end());
@@ -1408,7 +1412,9 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
   }
   if (d.enc.active && d.enc.png) {
     const EncDesc &e = d.enc;
-    for (uint32_t it = 0; it < e.h; it += 4) b.lists[L_PENC_ROW].push_back({I, it});
+    // the transformed image holds 16-bit samples (option "penc16"): its rows go to k_penc_filter16
+    const ListId rows = d.out_stride == 2 * d.out_w * d.out_c ? L_PENC_ROW16 : L_PENC_ROW;
+    for (uint32_t it = 0; it < e.h; it += 4) b.lists[rows].push_back({I, it});
     for (uint32_t it = 0; it < e.nblocks; it += 256) b.lists[L_PENC_PIECE].push_back({I, it});
     b.lists[L_ENC_IMG].push_back({I, 0});  // k_enc_scan: piece offsets
     b.lists[L_PENC_IMG].push_back({I, 0});

@@ -130,6 +130,8 @@ void launch_enc_write(hipStream_t st, const ImageDesc *imgs, const WgItem *list,
 void launch_enc_stuff(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // PNG re-encode (dg_penc.hip): 4 rows / 256 pieces / 1 image per workgroup
 void launch_penc_filter(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// ... the rows of images of 16-bit samples (option "penc16", dg_penc16.h)
+void launch_penc_filter16(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // dynamic (option "penc_dynamic"): count also builds the histograms; tree (1 image per workgroup) builds the
 // codes and chooses the block; count_dyn re-counts the pieces of the images that took the dynamic block
 void launch_penc_count(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic);

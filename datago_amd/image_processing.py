@@ -88,11 +88,12 @@ class ARAwareTransform:
     """Bucket table + the device context that applies it."""
 
     def __init__(self, cfg: ImageTransformConfig, device: int = 0, png16: bool = False, resize16: bool = False,
-                 penc_dynamic: bool = False):
+                 penc_dynamic: bool = False, penc16: bool = False):
         self.cfg = cfg
         self.penc_dynamic = penc_dynamic  # context option "penc_dynamic": PNG re-encode with per-image Huffman codes
         self.png16 = png16  # context option "png16": 16-bit PNGs of a bucket's size decode on the GPU
         self.resize16 = resize16  # context option "resize16": ... and every other 16-bit PNG resizes to its bucket
+        self.penc16 = penc16  # context option "penc16": ... and pre-encodes as a bit-depth-16 PNG (encode_format png)
         self.table = _lib.BucketTable(cfg.default_image_size, cfg.downsampling_ratio, cfg.min_aspect_ratio,
                                       cfg.max_aspect_ratio)
         bl = self.table.buckets()
@@ -116,7 +117,7 @@ class ARAwareTransform:
                                           max_aspect_ratio=c.max_aspect_ratio,
                                           image_to_rgb8=enc.img_to_rgb8, pre_encode_images=enc.encode_images,
                                           encode_format=int(enc.encode_format), jpeg_quality=enc.jpeg_quality,
-                                          png16=self.png16, resize16=self.resize16,
+                                          png16=self.png16, resize16=self.resize16, penc16=self.penc16,
                                           penc_dynamic=self.penc_dynamic)
         return self._ctx[key]
 
@@ -152,18 +153,20 @@ class ImagePayload:
 _plain_ctx: Dict[tuple, _lib.Context] = {}
 
 
-def _decode_ctx(device: int, enc: "ImageEncoding", png16: bool = False, resize16: bool = False) -> _lib.Context:
-    key = (device, enc.img_to_rgb8, enc.encode_images, int(enc.encode_format), enc.jpeg_quality, png16, resize16)
+def _decode_ctx(device: int, enc: "ImageEncoding", png16: bool = False, resize16: bool = False,
+                penc16: bool = False) -> _lib.Context:
+    key = (device, enc.img_to_rgb8, enc.encode_images, int(enc.encode_format), enc.jpeg_quality, png16, resize16,
+           penc16)
     if key not in _plain_ctx:
         _plain_ctx[key] = _lib.Context(device, image_to_rgb8=enc.img_to_rgb8, pre_encode_images=enc.encode_images,
                                        encode_format=int(enc.encode_format), jpeg_quality=enc.jpeg_quality,
-                                       png16=png16, resize16=resize16)
+                                       png16=png16, resize16=resize16, penc16=penc16)
     return _plain_ctx[key]
 
 
 def images_to_payloads(datas: List[bytes], img_tfm: Optional[ARAwareTransform], aspect_ratios: List[str],
                        encoding: ImageEncoding = ImageEncoding(), device: int = 0, png16: bool = False,
-                       resize16: bool = False) -> List[Tuple[int, Optional[ImagePayload]]]:
+                       resize16: bool = False, penc16: bool = False) -> List[Tuple[int, Optional[ImagePayload]]]:
     """Batched image_to_payload over coded bytes: one GPU batch.  Returns
     (status, payload) per image; status != 0 means the reference would have
     returned an ImageError (CORRUPT) or the format is outside the GPU path
@@ -171,7 +174,9 @@ def images_to_payloads(datas: List[bytes], img_tfm: Optional[ARAwareTransform], 
     transform; a transform carries its own): 16-bit PNGs decode to
     bit_depth-16 payloads whose data is native-endian u16.  resize16
     mirrors the context option of that name beside it (it only matters
-    under a transform, which carries its own flag)."""
+    under a transform, which carries its own flag).  penc16 likewise:
+    with pre-encoding as PNG a 16-bit image comes back as a bit-depth-16
+    PNG file (channels -1, bit_depth 16, is_encoded)."""
     if img_tfm is not None:
         ctx = img_tfm.context(encoding)
         forced = []
@@ -184,7 +189,7 @@ def images_to_payloads(datas: List[bytes], img_tfm: Optional[ARAwareTransform], 
                 raise KeyError("Aspect ratio not found in aspect ratio to size map")  # :334-336
             forced.append(k)
     else:
-        ctx = _decode_ctx(device, encoding, png16, resize16)
+        ctx = _decode_ctx(device, encoding, png16, resize16, penc16)
         forced = [-1] * len(datas)
     out = []
     for st, arr, m in ctx.decode_batch(datas, forced):
@@ -199,10 +204,10 @@ def images_to_payloads(datas: List[bytes], img_tfm: Optional[ARAwareTransform], 
 
 def image_to_payload(data: bytes, img_tfm: Optional[ARAwareTransform], aspect_ratio: str = "",
                      encoding: ImageEncoding = ImageEncoding(), device: int = 0, png16: bool = False,
-                     resize16: bool = False) -> ImagePayload:
+                     resize16: bool = False, penc16: bool = False) -> ImagePayload:
     """image_processing.rs:341-431 for one coded image.  Raises
     ValueError (the reference's ImageError) on undecodable input."""
-    st, p = images_to_payloads([data], img_tfm, [aspect_ratio], encoding, device, png16, resize16)[0]
+    st, p = images_to_payloads([data], img_tfm, [aspect_ratio], encoding, device, png16, resize16, penc16)[0]
     if st != _lib.DG_OK:
         raise ValueError(f"image decode failed: {_lib.STATUS_NAMES.get(st, st)}")
     return p
@@ -210,7 +215,7 @@ def image_to_payload(data: bytes, img_tfm: Optional[ARAwareTransform], aspect_ra
 
 def images_to_tensors(datas: List[bytes], img_tfm: Optional[ARAwareTransform], aspect_ratios: List[str],
                       encoding: ImageEncoding = ImageEncoding(), device: int = 0, png16: bool = False,
-                      resize16: bool = False):
+                      resize16: bool = False, penc16: bool = False):
     """images_to_payloads for a GPU training loop: the
     payload data stays in HBM as torch uint8 tensors written by the kernels,
     without the D2H copy and the two to three host copies of the Python
@@ -224,7 +229,7 @@ def images_to_tensors(datas: List[bytes], img_tfm: Optional[ARAwareTransform], a
                 raise KeyError("Aspect ratio not found in aspect ratio to size map")  # :334-336
             forced.append(k)
     else:
-        ctx = _decode_ctx(device, encoding, png16, resize16)
+        ctx = _decode_ctx(device, encoding, png16, resize16, penc16)
         forced = [-1] * len(datas)
     return ctx.decode_batch_torch(datas, forced)
 

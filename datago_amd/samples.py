@@ -13,7 +13,7 @@ out corrupt (known only after decoding) is skipped as the reference skips a
 failed load (worker_wds.rs:134-137) and the remaining payloads are re-run
 against the next reference.  Payloads outside the GPU path
 (DG_ERR_UNSUPPORTED: CMYK JPEG, 16-bit PNG and progressive JPEG unless
-their context options are set -- png16=True / resize16=True here ...) are
+their context options are set -- png16=True / resize16=True / penc16=True here ...) are
 returned with that status for the caller's CPU path; there is no CPU pixel
 path here.
 """
@@ -60,9 +60,9 @@ class Sample:              # structs.rs:242-280 (the fields this path fills)
 
 
 def _ctx(img_tfm: Optional[ARAwareTransform], encoding: ImageEncoding, device: int,
-         png16: bool = False, resize16: bool = False) -> _lib.Context:
+         png16: bool = False, resize16: bool = False, penc16: bool = False) -> _lib.Context:
     from .image_processing import _decode_ctx
-    return img_tfm.context(encoding) if img_tfm is not None else _decode_ctx(device, encoding, png16, resize16)
+    return img_tfm.context(encoding) if img_tfm is not None else _decode_ctx(device, encoding, png16, resize16, penc16)
 
 
 def _payload(arr, m) -> ImagePayload:
@@ -72,8 +72,8 @@ def _payload(arr, m) -> ImagePayload:
 
 
 def _aligned_batch(datas: List[bytes], img_tfm: Optional[ARAwareTransform], encodings: List[ImageEncoding],
-                   device: int = 0, png16: bool = False, resize16: bool = False
-                   ) -> List[Tuple[int, Optional[ImagePayload]]]:
+                   device: int = 0, png16: bool = False, resize16: bool = False,
+                   penc16: bool = False) -> List[Tuple[int, Optional[ImagePayload]]]:
     """Decode/transform a sample's payloads in order with reference-first
     alignment.  encodings[i] may differ per payload (DB masks)."""
     n = len(datas)
@@ -90,7 +90,7 @@ def _aligned_batch(datas: List[bytes], img_tfm: Optional[ARAwareTransform], enco
             groups.setdefault((e.encode_images, e.img_to_rgb8, int(e.encode_format), e.jpeg_quality), []).append(j)
         res: Dict[int, tuple] = {}
         for js in groups.values():
-            ctx = _ctx(img_tfm, encodings[todo[js[0]]], device, png16, resize16)
+            ctx = _ctx(img_tfm, encodings[todo[js[0]]], device, png16, resize16, penc16)
             for j, r in zip(js, ctx.decode_batch([datas[todo[j]] for j in js], [forced[j] for j in js])):
                 res[j] = r
         if key_idx is not None or table is None:
@@ -123,13 +123,14 @@ def _aligned_batch(datas: List[bytes], img_tfm: Optional[ARAwareTransform], enco
 
 def process_sample(sample: TarballSample, img_tfm: Optional[ARAwareTransform], encoding: ImageEncoding,
                    extension_reference_image: str = "jpg", device: int = 0, png16: bool = False,
-                   resize16: bool = False) -> Optional[Sample]:
+                   resize16: bool = False, penc16: bool = False) -> Optional[Sample]:
     """worker_wds.rs:19-171 for one tarball sample (members sorted
     reference-first by the generator, generator_wds.rs:154-166).  Returns
     None where the reference returns Err(()).  png16: 16-bit PNG members
     (depth maps, masks) decode on the GPU to bit_depth-16 payloads (a
     transform carries its own flags: with resize16 a depth map lands on
-    its reference image's bucket)."""
+    its reference image's bucket, with penc16 it is pre-encoded as a
+    bit-depth-16 PNG beside its photo)."""
     if not sample.content:
         return None
     sample_id = os.path.splitext(os.path.basename(sample.content[0].filename))[0]
@@ -145,7 +146,7 @@ def process_sample(sample: TarballSample, img_tfm: Optional[ARAwareTransform], e
             imgs.append(item)
         elif ext in TEXT_TYPES:
             attributes[ext] = item.buffer.decode("utf-8", errors="replace")
-    res = _aligned_batch([f.buffer for f in imgs], img_tfm, [encoding] * len(imgs), device, png16, resize16)
+    res = _aligned_batch([f.buffer for f in imgs], img_tfm, [encoding] * len(imgs), device, png16, resize16, penc16)
     final: Optional[Sample] = None
     for item, (st, p) in zip(imgs, res):
         if st == _lib.DG_ERR_UNSUPPORTED:
@@ -170,7 +171,8 @@ def process_sample(sample: TarballSample, img_tfm: Optional[ARAwareTransform], e
 
 def process_db_sample(sample_id: str, image: bytes, masks: Dict[str, bytes], additional_images: Dict[str, bytes],
                       img_tfm: Optional[ARAwareTransform], encoding: ImageEncoding,
-                      device: int = 0, png16: bool = False, resize16: bool = False) -> Optional[Sample]:
+                      device: int = 0, png16: bool = False, resize16: bool = False,
+                      penc16: bool = False) -> Optional[Sample]:
     """worker_http.rs:113-264: the image first (its output size fixes the
     aspect ratio), then the image-type latents with the same encoding and the
     masks as PNG without RGB conversion (:186-192).  Any failure fails the
@@ -180,7 +182,7 @@ def process_db_sample(sample_id: str, image: bytes, masks: Dict[str, bytes], add
     names = ["image"] + list(additional_images) + list(masks)
     datas = [image] + list(additional_images.values()) + list(masks.values())
     encs = [encoding] * (1 + len(additional_images)) + [mask_enc] * len(masks)
-    res = _aligned_batch(datas, img_tfm, encs, device, png16, resize16)
+    res = _aligned_batch(datas, img_tfm, encs, device, png16, resize16, penc16)
     if any(st not in (_lib.DG_OK, _lib.DG_ERR_UNSUPPORTED) for st, _ in res):
         return None
     s = Sample(sample_id, "db", res[0][1] if res[0][0] == _lib.DG_OK else ImagePayload())

@@ -47,7 +47,8 @@ typedef enum dg_status {
   DG_OK = 0,
   DG_ERR_UNSUPPORTED = 1, /* valid image the GPU path does not decode (arithmetic, 12-bit,
                              CMYK, non-JPEG/PNG...; 16-bit PNG unless option "png16" is set,
-                             and then still one that needs the resize or an encoder):
+                             and then still one that needs the resize or an encoder unless
+                             "resize16" / "penc16" are set too):
                              caller keeps its CPU path */
   DG_ERR_CORRUPT = 2,     /* maps to image::ImageError::Decoding: drop the sample */
   DG_ERR_OOM = 3,         /* device or host allocation failed */
@@ -263,7 +264,8 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 dropped (meta 3 / 8), and the encoders take the result.  Still DG_ERR_UNSUPPORTED
  *                 (dg_last_error says which): a 16-bit image whose size differs from its bucket's
  *                 (the reference resizes it with image's own f32 Lanczos3: option "resize16"), and one
- *                 that would reach an encoder as 16-bit (pre_encode_images without image_to_rgb8)
+ *                 that would reach an encoder as 16-bit (pre_encode_images without image_to_rgb8;
+ *                 option "penc16" takes it into the PNG encoder)
  *   "resize16"    1 = with "png16", a 16-bit PNG whose size differs from its bucket's (the closest or a
  *                 forced one) is resized to it on the GPU (default 0: DG_ERR_UNSUPPORTED).  The
  *                 resize is the image crate's resize_to_fill(w, h, Lanczos3), as the reference
@@ -272,6 +274,19 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 DESIGN.md "16-bit resize").  meta.width / height are the bucket's, bit_depth 16,
  *                 nbytes = 2 * width * height * channels; image_to_rgb8 converts the resized samples
  *                 and the encoders then take them.  16-bit into an encoder stays DG_ERR_UNSUPPORTED
+ *                 unless "penc16" is set
+ *   "penc16"      1 = with "png16" (and "resize16" for an image that is not its bucket's size), a 16-bit
+ *                 PNG under pre_encode_images with encode_format png, without image_to_rgb8, comes back
+ *                 as a bit-depth-16 PNG of the transformed samples, as the reference's PngEncoder writes an
+ *                 ImageLuma16 / LumaA16 / Rgb16 / Rgba16: colour type 0 / 4 / 2 / 6 (a resized LA16 image
+ *                 stays colour type 4), samples high byte first, filters over 2 x channels bytes per pixel,
+ *                 the rest of the file as for 8-bit images (DESIGN.md "PNG re-encode"; "penc_dynamic"
+ *                 applies and is recommended: filtered 16-bit data is larger than raw under the fixed
+ *                 block).  meta: channels -1, bit_depth 16, is_encoded 1, nbytes = the file's length;
+ *                 dg_output_size reports the bound of the doubled byte count.  Default 0:
+ *                 DG_ERR_UNSUPPORTED as before.  With encode_format jpeg a 16-bit image stays
+ *                 DG_ERR_UNSUPPORTED (image's JpegEncoder rejects 16-bit colour types; the reference drops
+ *                 the sample).  8-bit images and image_to_rgb8 contexts are untouched
  *   "penc_dynamic" 1 = PNG re-encode (pre_encode_images with encode_format png): an image whose DEFLATE
  *                 block is strictly shorter under a Huffman code built from its own histogram takes a
  *                 dynamic block (RFC 1951 3.2.7; DESIGN.md "PNG re-encode" states the bytes); every other
