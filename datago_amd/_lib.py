@@ -329,7 +329,8 @@ class Context:
                  downsampling_ratio: int = 0, min_aspect_ratio: float = 0.0, max_aspect_ratio: float = 0.0,
                  image_to_rgb8: bool = False, pre_encode_images: bool = False, encode_format: int = 0,
                  jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False,
-                 resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False):
+                 resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False,
+                 jenc_optimize: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -352,6 +353,8 @@ class Context:
             self.set_option("penc16", 1)
         if penc_dynamic:  # PNG re-encode: per-image Huffman codes where they make the file shorter
             self.set_option("penc_dynamic", 1)
+        if jenc_optimize:  # JPEG re-encode: per-image Huffman tables (libjpeg's optimize_coding rule)
+            self.set_option("jenc_optimize", 1)
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

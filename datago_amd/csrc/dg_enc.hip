@@ -13,12 +13,20 @@
 //                neighbouring blocks ever see two writers)
 //   k_enc_stuff  one workgroup per image: header copy, 0xFF -> 0xFF 0x00
 //                stuffing with a block-wide scan, 1-bit padding, EOI
+// Context option "jenc_optimize" puts two passes between fdct and count:
+//   k_enc_hist   one thread per block: the symbols of each table pair counted
+//                in LDS, then added to the image's histogram
+//   k_enc_tree   one workgroup per image, one wave per table: libjpeg's
+//                optimal table (dg_jenc_tree.h), the image's EncTables and DHT
+//                segments; count / write then read the image's own tables and
+//                stuff puts the DHTs between the host's DQTs and SOS
 // oracle/jpeg_enc_oracle.c is the CPU restatement the tests compare against
 // byte for byte.  All of it is integer/byte work except the colour
 // conversion and the quantisation divide (f32, IEEE, no contraction).
 #include <hip/hip_runtime.h>
 
 #include "dg_types.h"
+#include "dg_jenc_tree.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -148,8 +156,9 @@ __device__ __forceinline__ uint32_t magnitude_bits(int32_t v) {
 }
 
 // Visit the Huffman codes of block b: emit(code, len) then emit(bits, n) per symbol.
-template <class F>
-__device__ __forceinline__ void enc_block(const EncDesc &e, const EncTables *T, uint32_t b, F emit) {
+// Tab: EncTables, or EncSymbols to see the symbols themselves.
+template <class Tab, class F>
+__device__ __forceinline__ void enc_block(const EncDesc &e, const Tab *T, uint32_t b, F emit) {
   const DG_GLOBAL int16_t *co = gp<const int16_t>(e.coef) + (size_t)b * 64;
   const uint32_t c = b % e.ncomp;
   const int32_t prev = b >= e.ncomp ? (int32_t)(gp<const int16_t>(e.coef)[(size_t)(b - e.ncomp) * 64]) : 0;
@@ -178,6 +187,110 @@ __device__ __forceinline__ void enc_block(const EncDesc &e, const EncTables *T, 
     run = 0;
   }
   if (v63 == 0) emit(T->code[t + 1][0x00], T->len[t + 1][0x00]);
+}
+
+// In place of EncTables: code[t][sym] is t << 8 | sym and len[t][sym] is kSymLen, which no code or value has.
+constexpr uint32_t kSymLen = ~0u;
+struct EncSymbols {
+  struct CodeRow {
+    uint32_t t;
+    __device__ uint32_t operator[](uint32_t sym) const { return t << 8 | sym; }
+  };
+  struct Codes {
+    __device__ CodeRow operator[](uint32_t t) const { return {t}; }
+  } code;
+  struct LenRow {
+    __device__ uint32_t operator[](uint32_t) const { return kSymLen; }
+  };
+  struct Lens {
+    __device__ LenRow operator[](uint32_t) const { return {}; }
+  } len;
+};
+
+// Option "jenc_optimize".  One thread per block, the work list of k_enc_count:
+// a workgroup holds 256 consecutive blocks of one image.  Integer sums: the
+// histogram does not depend on the order of the adds.
+__global__ __launch_bounds__(256) void k_enc_hist(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  __shared__ uint32_t hist[kJencHistWords];
+  const WgItem it = list[blockIdx.x];
+  const ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  const EncDesc &e = im.enc;
+  if (!e.jopt) return;
+  for (uint32_t i = threadIdx.x; i < kJencHistWords; i += 256) hist[i] = 0;
+  __syncthreads();
+  const uint32_t b = it.item0 + threadIdx.x;
+  if (b < e.nblocks) {
+    const EncSymbols S = {};
+    enc_block(e, &S, b, [&](uint32_t v, uint32_t len) {
+      if (len != kSymLen) return;  // the value bits
+      const uint32_t t = v >> 8, sym = v & 255u;
+      atomicAdd(&hist[(t >> 1) * kJencHistPair + ((t & 1u) ? kJencDcSyms + sym : sym & (kJencDcSyms - 1))], 1u);
+    });
+  }
+  __syncthreads();
+  DG_GLOBAL uint32_t *gh = gp<uint32_t>(e.jopt);
+  for (uint32_t i = threadIdx.x; i < kJencHistWords; i += 256)
+    if (hist[i]) atomicAdd((uint32_t *)&gh[i], hist[i]);
+}
+
+// Option "jenc_optimize".  One workgroup per image, wave t builds table t (DC
+// luma, AC luma, DC chroma, AC chroma; two for one component).  Decide first,
+// write second: an image with a K.2 size above 32 in any table keeps the
+// standard tables and header.
+struct JencTreeSmem {
+  JtWork work[4];
+  JtOut out[4];
+};
+
+__global__ __launch_bounds__(256) void k_enc_tree(ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  __shared__ JencTreeSmem sm;
+  const WgItem it = list[blockIdx.x];
+  ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  EncDesc &e = im.enc;
+  if (e.png || !e.jopt) return;
+  const uint32_t t = threadIdx.x >> 6, lane = threadIdx.x & 63u, ntab = e.ncomp == 1 ? 2u : 4u;
+  EncTables *tab = (EncTables *)(uintptr_t)(e.jopt + kJencTabOff);
+  if (t < ntab) {
+    const DG_GLOBAL uint32_t *f = gp<const uint32_t>(e.jopt) + (t >> 1) * kJencHistPair + ((t & 1u) ? kJencDcSyms : 0u);
+    jt_build(
+        f, (t & 1u) ? 256u : kJencDcSyms, sm.work[t], sm.out[t], tab->code[t], tab->len[t], lane, 64u,
+        [] {  // one wave: its LDS operations complete in order; keep the compiler from moving them
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+          __builtin_amdgcn_wave_barrier();
+        },
+        [](uint64_t &a, uint64_t &b) {
+          for (int o = 32; o; o >>= 1) {
+            const uint64_t a2 = __shfl_xor((unsigned long long)a, o), b2 = __shfl_xor((unsigned long long)b, o);
+            const uint64_t lo = a < a2 ? a : a2, hi = a < a2 ? a2 : a, bb = b < b2 ? b : b2;
+            a = lo;
+            b = hi < bb ? hi : bb;
+          }
+        });
+  }
+  __syncthreads();
+  uint32_t fallback = 0, off[5] = {0, 0, 0, 0, 0};
+  for (uint32_t k = 0; k < ntab; k++) {
+    fallback |= sm.out[k].fallback;
+    off[k + 1] = off[k] + jt_dht_bytes(sm.out[k]);
+  }
+  if (fallback) {
+    if (threadIdx.x == 0) {
+      e.tab = e.tab_std;
+      e.hdr_len = e.hdr_std;
+      e.dht_len = 0;
+      e.dyn = 0;
+    }
+    return;
+  }
+  if (t < ntab) jt_dht(sm.out[t], (t & 1u) << 4 | t >> 1, gp<uint8_t>(e.jopt + kJencDhtOff) + off[t], lane, 64u);
+  if (threadIdx.x == 0) {
+    e.tab = (uint64_t)(uintptr_t)tab;
+    e.dht_len = off[ntab];
+    e.hdr_len = e.hdr_pre + off[ntab] + (e.hdr_std - e.hdr_sos);
+    e.dyn = 1;
+  }
 }
 
 __global__ __launch_bounds__(256) void k_enc_count(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
@@ -258,7 +371,14 @@ __global__ __launch_bounds__(1024) void k_enc_stuff(ImageDesc *__restrict__ imgs
   const uint32_t t = threadIdx.x;
   DG_GLOBAL uint8_t *out = gp<uint8_t>(e.out);
   const DG_GLOBAL uint8_t *hdr = gp<const uint8_t>(e.hdr);
-  for (uint32_t i = t; i < e.hdr_len; i += 1024) out[i] = hdr[i];
+  if (e.dyn) {  // option "jenc_optimize": the host's SOI .. DQT, the image's DHTs (k_enc_tree), the host's SOS
+    const DG_GLOBAL uint8_t *dht = gp<const uint8_t>(e.jopt + kJencDhtOff);
+    const uint32_t pre = e.hdr_pre, mid = pre + e.dht_len;
+    for (uint32_t i = t; i < e.hdr_len; i += 1024)
+      out[i] = i < pre ? hdr[i] : i < mid ? dht[i - pre] : hdr[e.hdr_sos + (i - mid)];
+  } else {
+    for (uint32_t i = t; i < e.hdr_len; i += 1024) out[i] = hdr[i];
+  }
   const uint32_t tb = e.total_bits, nbytes = (tb + 7) / 8, rem = tb & 7u;
   const DG_GLOBAL uint8_t *sb = gp<const uint8_t>(e.words);
   uint32_t base = e.hdr_len;
@@ -306,6 +426,12 @@ __global__ __launch_bounds__(1024) void k_enc_stuff(ImageDesc *__restrict__ imgs
 
 void launch_enc_fdct(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   if (nwg) hipLaunchKernelGGL(k_enc_fdct, dim3(nwg), dim3(256), 0, st, imgs, list);
+}
+void launch_enc_hist(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_enc_hist, dim3(nwg), dim3(256), 0, st, imgs, list);
+}
+void launch_enc_tree(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_enc_tree, dim3(nwg), dim3(256), 0, st, imgs, list);
 }
 void launch_enc_count(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   if (nwg) hipLaunchKernelGGL(k_enc_count, dim3(nwg), dim3(256), 0, st, imgs, list);

@@ -242,7 +242,9 @@ constexpr uint32_t kAlphaPoints = 3;  // before call 1, between the calls, after
 // Annex K tables scaled by quality.  Per image: k_enc_fdct (colour + FDCT +
 // quantisation per MCU), k_enc_count (bits per block), k_enc_scan (bit
 // offsets), k_enc_write (codes OR-ed into a zeroed bit buffer), k_enc_stuff
-// (header, 0xFF00 stuffing, padding, EOI).
+// (header, 0xFF00 stuffing, padding, EOI).  Option "jenc_optimize": k_enc_hist
+// and k_enc_tree after fdct give each image EncTables and DHT segments of its
+// own (dg_jenc_tree.h).
 struct EncTables {
   uint16_t code[4][256];  // DC luma, AC luma, DC chroma, AC chroma
   uint8_t len[4][256];
@@ -265,7 +267,14 @@ struct EncDesc {
                          // nblocks = 1 KiB pieces, bits = piece bit lengths
   uint32_t hdr_bits;     // png: bits in front of the first token: 3, or the dynamic block's header (k_penc_tree)
   uint16_t dyn, eob_len; // png: 1 = dynamic block (k_penc_tree chose it); bits of the end-of-block code (7 fixed)
+                         // jpeg: dyn 1 = the image's own Huffman tables and DHT segments (k_enc_tree)
   uint64_t aux;                  // png: Adler-32 partials per piece (uint32 x 2)
+  // jpeg, option "jenc_optimize" (dg_jenc_tree.h): jopt = the image's histogram / EncTables / DHT region (0: option
+  // off).  k_enc_tree sets tab, hdr_len, dht_len and dyn = 1 for an image that takes its own tables, and puts
+  // tab_std, hdr_std and dyn = 0 back for one that keeps the standard ones.
+  uint64_t jopt, tab_std;
+  uint32_t hdr_std, dht_len;
+  uint16_t hdr_pre, hdr_sos;     // the host's header: bytes in front of its DHT segments; offset of its SOS segment
   uint8_t q[2][64];    // quantisation tables, natural order
 };
 

@@ -78,7 +78,8 @@ void jpeg_enc_qtables(int quality, uint8_t q[2][64]) {
   }
 }
 
-std::vector<uint8_t> jpeg_enc_header(uint32_t w, uint32_t h, int ncomp, int quality) {
+std::vector<uint8_t> jpeg_enc_header(uint32_t w, uint32_t h, int ncomp, int quality, uint32_t *dht_off,
+                                     uint32_t *sos_off) {
   std::vector<uint8_t> o = {0xFF, 0xD8};
   segment(o, 0xE0, {'J', 'F', 'I', 'F', 0, 1, 2, 0, 0, 1, 0, 1, 0, 0});
   std::vector<uint8_t> sof = {8, (uint8_t)(h >> 8), (uint8_t)h, (uint8_t)(w >> 8), (uint8_t)w, (uint8_t)ncomp};
@@ -98,6 +99,7 @@ std::vector<uint8_t> jpeg_enc_header(uint32_t w, uint32_t h, int ncomp, int qual
   const uint8_t *bits[4] = {kDcLumaBits, kAcLumaBits, kDcChromaBits, kAcChromaBits};
   const uint8_t *vals[4] = {kDcVals, kAcLumaVals, kDcVals, kAcChromaVals};
   const uint8_t cls[4] = {0x00, 0x10, 0x01, 0x11};
+  if (dht_off) *dht_off = (uint32_t)o.size();
   for (int t = 0; t < (ncomp == 1 ? 2 : 4); t++) {
     std::vector<uint8_t> d = {cls[t]};
     int nv = 0;
@@ -108,6 +110,7 @@ std::vector<uint8_t> jpeg_enc_header(uint32_t w, uint32_t h, int ncomp, int qual
     d.insert(d.end(), vals[t], vals[t] + nv);
     segment(o, 0xC4, d);
   }
+  if (sos_off) *sos_off = (uint32_t)o.size();
   std::vector<uint8_t> sos = {(uint8_t)ncomp};
   for (int c = 0; c < ncomp; c++) {
     sos.push_back((uint8_t)(c + 1));
@@ -131,7 +134,10 @@ void jpeg_enc_tables(EncTables &t) {
 uint64_t jpeg_enc_bound(uint32_t w, uint32_t h, uint32_t C) {
   const uint64_t ncomp = C <= 2 ? 1 : 3;
   const uint64_t blocks = (uint64_t)((w + 7) / 8) * ((h + 7) / 8) * ncomp;
-  return 1024 + blocks * 420;  // a block codes to <= 1665 bits; stuffing at most doubles it
+  // A block codes to <= 1665 bits; stuffing at most doubles it.  Option "jenc_optimize" keeps both terms: an
+  // optimised DHT lists a subset of the standard one's symbols, so the header never grows, and its code lengths
+  // stay at or below 16 like the standard ones, so the per-block bound holds.
+  return 1024 + blocks * 420;
 }
 
 }  // namespace dg

@@ -15,8 +15,10 @@ namespace dg {
 
 // quality in [1, 100] -> natural-order tables (0 luma, 1 chroma), clamped to [1, 255]
 void jpeg_enc_qtables(int quality, uint8_t q[2][64]);
-// header bytes for a w x h image with ncomp (1 or 3) components
-std::vector<uint8_t> jpeg_enc_header(uint32_t w, uint32_t h, int ncomp, int quality);
+// header bytes for a w x h image with ncomp (1 or 3) components; dht_off / sos_off: where its DHT segments and
+// its SOS segment begin (option "jenc_optimize" puts per-image DHTs between the two parts, dg_jenc_tree.h)
+std::vector<uint8_t> jpeg_enc_header(uint32_t w, uint32_t h, int ncomp, int quality, uint32_t *dht_off = nullptr,
+                                     uint32_t *sos_off = nullptr);
 // code/length of every symbol of the four standard tables
 void jpeg_enc_tables(EncTables &t);
 // bytes the caller must provide for an encoded w x h x C image

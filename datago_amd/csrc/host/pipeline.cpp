@@ -427,6 +427,18 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     penc_dynamic_ = v != 0;
     return DG_OK;
   }
+  if (k == "jenc_optimize") {
+    // JPEG re-encode (pre_encode_images, encode_format jpeg): 1 = every image is
+    // coded with Huffman tables built from its own symbol counts by libjpeg's
+    // jpeg_gen_optimal_table rule (dg_jenc_tree.h) and carries them in its DHT
+    // segments; everything else in the file is unchanged.  An image in which
+    // the rule meets a code size above 32, and every image with 0 (the
+    // default), takes the Annex K tables byte for byte as before.  Nothing
+    // changes for PNG re-encoding.
+    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
+    jenc_optimize_ = v != 0;
+    return DG_OK;
+  }
   if (k == "prog_lanes") {  // dg_decode_one: progressive batches in flight on the progressive slots; 0: mixed in
     if (v < 0 || v > kProgSlots) return opt_error(k, v, "valid unless v < 0 || v > " + std::to_string(kProgSlots));
     prog_lanes_ = (int)v;
@@ -1855,6 +1867,10 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   if (b.any_enc) {
     HIPCHK(hipMemsetAsync((char *)sl.scratch.p + b.words_off, 0, b.words_bytes, sl.st));
     launch_enc_fdct(sl.st, dd, lst(L_ENC_MCU), cnt(L_ENC_MCU));
+    if (b.jenc_opt) {  // per-image Huffman tables: count, write and stuff then go by the image's own
+      launch_enc_hist(sl.st, dd, lst(L_ENC_BLK), cnt(L_ENC_BLK));
+      launch_enc_tree(sl.st, dm, lst(L_ENC_IMG), cnt(L_ENC_IMG));
+    }
     launch_enc_count(sl.st, dd, lst(L_ENC_BLK), cnt(L_ENC_BLK));
     launch_penc_filter(sl.st, dd, lst(L_PENC_ROW), cnt(L_PENC_ROW));
     launch_penc_filter16(sl.st, dd, lst(L_PENC_ROW16), cnt(L_PENC_ROW16));

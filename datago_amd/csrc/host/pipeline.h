@@ -91,6 +91,7 @@ struct Batch {
   size_t blob_off = 0;
   bool any_png = false, any_alpha = false, any_enc = false;
   bool penc_dyn = false;  // a PNG re-encode with option "penc_dynamic": histogram, k_penc_tree, dynamic count / write
+  bool jenc_opt = false;  // a JPEG re-encode with option "jenc_optimize": k_enc_hist, k_enc_tree, per-image tables
   bool any_fused = false;  // some image's IDCT runs inside k_huff_write
   uint32_t idct_cap = 0;   // entries of BatchFlags::idct_list
   uint32_t v_tile = 0;     // rows per k_resize_vt tile the V lists were built for
@@ -527,6 +528,7 @@ class Context {
   bool resize16_ = false;               // option "resize16": ... and resize to their bucket (dg_resize16.hip)
   bool penc16_ = false;                 // option "penc16": ... and go into the PNG re-encoder as 16-bit samples (dg_penc16.h)
   bool penc_dynamic_ = false;           // option "penc_dynamic": PNG re-encode with per-image Huffman codes where shorter
+  bool jenc_optimize_ = false;          // option "jenc_optimize": JPEG re-encode with per-image Huffman tables
   bool prog_serial_ = false;            // option "prog_serial": serial reader for every scan (A/B)
   bool prog_pipe_ = true;               // option "prog_pipe": all scans in one pipelined launch (0: one launch per level)
   int prog_chain_ = 100;                // option "prog_chain": chain dependency groups costing <= this % of the longest scan

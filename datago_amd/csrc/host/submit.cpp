@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "../dg_entropy.h"
+#include "../dg_jenc_tree.h"
 #include "../dg_pixel.h"
 #include "../kernels.h"
 #include "pipeline_util.h"
@@ -135,7 +136,8 @@ struct Offs {
   size_t final_off, tmp, out, ds, mk, chunk, stage;
   size_t zs, raw, unf, pal;
   size_t tout, ecoef, ebits, ewords, hdr, eaux;  // JPEG / PNG re-encode
-  size_t etab;  // PNG, option "penc_dynamic": bytes of histogram / code table at the head of ewords
+  size_t etab;  // PNG, option "penc_dynamic": bytes of histogram / code table at the head of ewords;
+                // JPEG, option "jenc_optimize": bytes of histogram / EncTables / DHT segments there
   // alpha programs: buffer = dst of pass `stage` (-1: the decoded image), byte offset
   int aop_stage[kAlphaPoints];
   size_t aop_off[kAlphaPoints];
@@ -936,14 +938,23 @@ void Context::layout_output_and_encode(const SubmitArgs &a, int i, int last_stag
     uint8_t q[2][64];
     jpeg_enc_qtables(qual, q);
     memcpy(e.q, q, sizeof(q));
-    const std::vector<uint8_t> hdr = jpeg_enc_header(p.out_w, p.out_h, (int)e.ncomp, qual);
-    e.hdr_len = (uint32_t)hdr.size();
+    uint32_t dht_off = 0, sos_off = 0;
+    const std::vector<uint8_t> hdr = jpeg_enc_header(p.out_w, p.out_h, (int)e.ncomp, qual, &dht_off, &sos_off);
+    e.hdr_len = e.hdr_std = (uint32_t)hdr.size();
+    e.hdr_pre = (uint16_t)dht_off;
+    e.hdr_sos = (uint16_t)sos_off;
+    e.dyn = 0;
     o.hdr = b.blob.size();
     b.blob.insert(b.blob.end(), hdr.begin(), hdr.end());
     o.tout = bl.L.take(p.img_bytes + 16, 256);
     o.ecoef = bl.L.take((size_t)e.nblocks * 128, 256);
     o.ebits = bl.L.take((size_t)e.nblocks * 4, 256);
     o.ewords = (size_t)(e.nblocks * 210ull + 64) / 4 * 4 + 16;  // size for now; placed with the batch's regions
+    // option "jenc_optimize": the image's histogram, EncTables and DHT segments (dg_jenc_tree.h) in front of its
+    // bit buffer, inside the region the batch zeroes
+    o.etab = jenc_optimize_ ? kJencOptBytes : 0;
+    o.ewords += o.etab;
+    b.jenc_opt = b.jenc_opt || jenc_optimize_;
     b.any_enc = true;
   }
 }
@@ -1103,6 +1114,7 @@ void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const Bat
       e.bits = (uint64_t)(uintptr_t)(S + o.ebits);
       e.words = (uint64_t)(uintptr_t)(S + o.ewords + o.etab);
       if (e.png) e.tab = o.etab ? (uint64_t)(uintptr_t)(S + o.ewords) : 0;
+      else e.jopt = o.etab ? (uint64_t)(uintptr_t)(S + o.ewords) : 0;
       e.aux = o.eaux ? (uint64_t)(uintptr_t)(S + o.eaux) : 0;
       e.hdr = o.hdr + 1;  // blob offset + 1: made absolute with the meta buffer
     }
@@ -1443,7 +1455,7 @@ dg_status Context::stage_and_upload(const SubmitArgs &a, Slot &sl, Batch &b, con
     if (d.fmt == kFmtPng && d.png.pal) d.png.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.png.pal - 1);
     if (d.enc.active) {
       d.enc.hdr = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.enc.hdr - 1);
-      if (!d.enc.png) d.enc.tab = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + b.enctab_off);
+      if (!d.enc.png) d.enc.tab = d.enc.tab_std = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + b.enctab_off);
     }
   }
   size_t stage_bytes = b.meta_bytes + (a.host_io ? bl.IN.off : 0);

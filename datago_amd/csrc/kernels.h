@@ -125,6 +125,10 @@ namespace dg {
 // scan / stuff: one 1024-thread workgroup per image
 void launch_enc_fdct(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_enc_count(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// option "jenc_optimize": hist = 256 blocks per workgroup (count's list), tree = one image per workgroup (scan's
+// list) builds the image's Huffman tables and DHT segments (dg_jenc_tree.h); both run between fdct and count
+void launch_enc_hist(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_enc_tree(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_enc_scan(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_enc_write(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_enc_stuff(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);

@@ -88,8 +88,9 @@ class ARAwareTransform:
     """Bucket table + the device context that applies it."""
 
     def __init__(self, cfg: ImageTransformConfig, device: int = 0, png16: bool = False, resize16: bool = False,
-                 penc_dynamic: bool = False, penc16: bool = False):
+                 penc_dynamic: bool = False, penc16: bool = False, jenc_optimize: bool = False):
         self.cfg = cfg
+        self.jenc_optimize = jenc_optimize  # context option "jenc_optimize": JPEG re-encode with per-image Huffman tables
         self.penc_dynamic = penc_dynamic  # context option "penc_dynamic": PNG re-encode with per-image Huffman codes
         self.png16 = png16  # context option "png16": 16-bit PNGs of a bucket's size decode on the GPU
         self.resize16 = resize16  # context option "resize16": ... and every other 16-bit PNG resizes to its bucket
@@ -118,7 +119,7 @@ class ARAwareTransform:
                                           image_to_rgb8=enc.img_to_rgb8, pre_encode_images=enc.encode_images,
                                           encode_format=int(enc.encode_format), jpeg_quality=enc.jpeg_quality,
                                           png16=self.png16, resize16=self.resize16, penc16=self.penc16,
-                                          penc_dynamic=self.penc_dynamic)
+                                          penc_dynamic=self.penc_dynamic, jenc_optimize=self.jenc_optimize)
         return self._ctx[key]
 
 

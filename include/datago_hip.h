@@ -292,6 +292,16 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 dynamic block (RFC 1951 3.2.7; DESIGN.md "PNG re-encode" states the bytes); every other
  *                 image keeps the fixed block.  Default 0: the fixed block always, byte for byte as
  *                 before.  The bound dg_output_size reports is the same; JPEG re-encoding ignores it
+ *   "jenc_optimize" 1 = JPEG re-encode (pre_encode_images with encode_format jpeg): every image is coded
+ *                 with Huffman tables built from its own symbol counts by libjpeg's jpeg_gen_optimal_table
+ *                 rule (T.81 K.2 + K.3, what optimize_coding gives; DESIGN.md "JPEG re-encode" states it)
+ *                 and carries them in its four DHT segments (two for one component); the coefficients and
+ *                 every other byte of the file are the same, about 10% fewer bytes for a photo.  An image
+ *                 in which the rule meets a code size above 32 keeps the Annex K tables.  Default 0: the
+ *                 Annex K tables always, byte for byte as before (what the reference writes).  Any other
+ *                 value: DG_ERR_INVALID.  The bound dg_output_size reports is the same, meta as before
+ *                 (channels -1, is_encoded 1, nbytes = the file's length); PNG re-encoding ignores it and
+ *                 16-bit images stay DG_ERR_UNSUPPORTED at the JPEG encoder
  *   "prog_split"  1 = progressive members of a dg_submit run in the progressive aggregate (default 1,
  *                 see dg_wait_ready); 0 = in the submission's own batch
  *   "prog_batch"  progressive aggregate: launched once it holds this many images (default 2048)
