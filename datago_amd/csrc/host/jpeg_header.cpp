@@ -40,7 +40,7 @@ static void fail(JpegHeader &h, int st, const char *why) {
   h.why = why;
 }
 
-void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h) {
+void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v2) {
   h = JpegHeader();
   if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(h, JH_CORRUPT, "not a JPEG (no SOI)");
   bool saw_sof = false;
@@ -230,7 +230,8 @@ void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h) {
       const JpegComponent &k = h.comp[c];
       if (h.hmax % k.h || h.vmax % k.v) return fail(h, JH_UNSUPPORTED, "fractional sampling ratio");
       int hr = h.hmax / k.h, vr = h.vmax / k.v;
-      if (!((hr == 1 && vr == 1) || (hr == 2 && vr == 1) || (hr == 2 && vr == 2)))
+      // h1v2 (4:4:0 and its mixed layouts) only behind context option jpeg_h1v2
+      if (!((hr == 1 && vr == 1) || (hr == 2 && vr == 1) || (hr == 2 && vr == 2) || (allow_h1v2 && hr == 1 && vr == 2)))
         return fail(h, JH_UNSUPPORTED, "chroma sampling other than 4:4:4/4:2:2/4:2:0");
       blocks += k.h * k.v;
     }

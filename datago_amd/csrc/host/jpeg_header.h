@@ -70,8 +70,10 @@ struct JpegHeader {
 };
 
 // Parse up to (and including) the SOS header.  Only touches bytes before the
-// entropy-coded segment plus the last two bytes (EOI check).
-void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h);
+// entropy-coded segment plus the last two bytes (EOI check).  allow_h1v2
+// (context option jpeg_h1v2) also accepts a component at the full horizontal
+// and half the vertical rate (4:4:0); without it such a file is JH_UNSUPPORTED.
+void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v2 = false);
 
 // Canonical Huffman code -> GPU lookup table (T.81 Annex C).  Returns false
 // for an over-subscribed code.

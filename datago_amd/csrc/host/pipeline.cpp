@@ -395,6 +395,17 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     png16_ = v != 0;
     return DG_OK;
   }
+  if (k == "jpeg_h1v2") {
+    // Colour JPEGs with a component at the full horizontal and half the
+    // vertical rate (4:4:0, what a lossless 90-degree rotation makes of 4:2:2;
+    // default off: DG_ERR_UNSUPPORTED, the caller's CPU decoder takes them).
+    // 1: parse_jpeg_header accepts them and upsample8 / upsample8_zune blend the
+    // two nearest plane rows 3:1 (kernels.hip).  dg_probe keeps describing the
+    // default options.
+    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
+    jpeg_h1v2_ = v != 0;
+    return DG_OK;
+  }
   if (k == "resize16") {
     // 16-bit PNGs that are not their bucket's size (default off:
     // DG_ERR_UNSUPPORTED).  1, together with "png16": they resize with the
@@ -1410,7 +1421,7 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
       p.status = DG_ERR_CORRUPT;
       return DG_OK;
     }
-    parse_jpeg_header(h, len, p.hdr);
+    parse_jpeg_header(h, len, p.hdr, jpeg_h1v2_);  // option "jpeg_h1v2"
     if (p.hdr.status != JH_OK) {
       p.status = p.hdr.status == JH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
       return DG_OK;

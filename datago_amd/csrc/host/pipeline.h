@@ -525,6 +525,7 @@ class Context {
   bool idct_fused_ = false;             // option "idct_fused" (measured 7x slower k_huff_write: off)
   bool progressive_ = true;             // option "progressive"
   bool png16_ = false;                  // option "png16": 16-bit PNGs decode on the GPU
+  bool jpeg_h1v2_ = false;              // option "jpeg_h1v2": 4:4:0-style JPEGs decode on the GPU
   bool resize16_ = false;               // option "resize16": ... and resize to their bucket (dg_resize16.hip)
   bool penc16_ = false;                 // option "penc16": ... and go into the PNG re-encoder as 16-bit samples (dg_penc16.h)
   bool penc_dynamic_ = false;           // option "penc_dynamic": PNG re-encode with per-image Huffman codes where shorter

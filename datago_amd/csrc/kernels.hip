@@ -1349,7 +1349,24 @@ __device__ __forceinline__ void upsample8(P pl, uint32_t stride, uint32_t hr, ui
     }
     return;
   }
-  if (hr == 1) {  // 4:4:4 component (vr is 1 too for the supported samplings)
+  if (hr == 1 && vr == 2) {
+    // h1v2 component (option "jpeg_h1v2"; libjpeg h1v2_fancy_upsample): the near
+    // row 3:1 with the row above (even y, bias 1) or below (odd y, bias 2),
+    // clamped to the component's rows; no box filter for narrow images
+    const uint32_t r = y >> 1;
+    int32_t rn = (y & 1) ? (int32_t)r + 1 : (int32_t)r - 1;
+    rn = rn < 0 ? 0 : (rn > (int32_t)dsh - 1 ? (int32_t)dsh - 1 : rn);
+    const u32x2 v0 = *(const DG_GLOBAL u32x2 *)(pl + (size_t)__umul24(r, stride) + x0);
+    const u32x2 v1 = *(const DG_GLOBAL u32x2 *)(pl + (size_t)__umul24((uint32_t)rn, stride) + x0);
+    const int32_t bias = 1 + (int32_t)(y & 1);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      o[k] = (3 * (int32_t)((v0.x >> (8 * k)) & 0xFF) + (int32_t)((v1.x >> (8 * k)) & 0xFF) + bias) >> 2;
+      o[k + 4] = (3 * (int32_t)((v0.y >> (8 * k)) & 0xFF) + (int32_t)((v1.y >> (8 * k)) & 0xFF) + bias) >> 2;
+    }
+    return;
+  }
+  if (hr == 1) {  // 4:4:4 component
     u32x2 v = *(const DG_GLOBAL u32x2 *)(pl + (size_t)__umul24(y, stride) + x0);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -1470,6 +1487,22 @@ __device__ __forceinline__ void upsample8_zune(P pl, uint32_t stride, uint32_t h
       }
       o[2 * k] = ev;
       o[2 * k + 1] = od;
+    }
+    return;
+  }
+  if (hr == 1 && vr == 2) {
+    // h1v2 component (option "jpeg_h1v2"): zune-jpeg's upsample_vertical as
+    // recalled from the crate's source (parity-unpinned like the rest of this
+    // mode): the vertical half of h2v2 above, no horizontal step; rows clamp
+    // to the MCU-padded plane
+    const uint32_t r = y >> 1;
+    const uint32_t rn = (y & 1) ? (r + 1 < ph ? r + 1 : r) : (r > 0 ? r - 1 : 0);
+    const u32x2 v0 = *(const DG_GLOBAL u32x2 *)(pl + (size_t)__umul24(r, stride) + x0);
+    const u32x2 v1 = *(const DG_GLOBAL u32x2 *)(pl + (size_t)__umul24(rn, stride) + x0);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      o[k] = (3 * (int32_t)((v0.x >> (8 * k)) & 0xFF) + 2 + (int32_t)((v1.x >> (8 * k)) & 0xFF)) >> 2;
+      o[k + 4] = (3 * (int32_t)((v0.y >> (8 * k)) & 0xFF) + 2 + (int32_t)((v1.y >> (8 * k)) & 0xFF)) >> 2;
     }
     return;
   }
@@ -1810,7 +1843,14 @@ enum FillClass : int {
   FC_420 = 1, FC_420_Z = 2,  // Y h2v2, Cb/Cr h1v1 as chroma records; libjpeg fancy / zune
   FC_422 = 3, FC_422_Z = 4,  // Y h2v1, Cb/Cr h1v1 as chroma records
   FC_444 = 5, FC_444_Z = 6,  // all components at full rate (plain planes)
+  FC_440 = 7, FC_440_Z = 8,  // Y h1v2, Cb/Cr h1v1 (plain planes; option "jpeg_h1v2")
 };
+// zune semantics; chroma subsampling of a class: 0 none, 1 h2v1, 2 h2v2, 3 h1v2
+constexpr bool fc_zune(int fc) { return fc == FC_420_Z || fc == FC_422_Z || fc == FC_444_Z || fc == FC_440_Z; }
+constexpr int fc_ss(int fc) {
+  return (fc == FC_420 || fc == FC_420_Z) ? 2 : (fc == FC_422 || fc == FC_422_Z) ? 1
+         : (fc == FC_440 || fc == FC_440_Z) ? 3 : 0;
+}
 
 __device__ __forceinline__ int fill_class(const ImageDesc &im) {
   if (im.ncomp != 3 || im.colorspace != CS_YCC) return FC_GENERIC;
@@ -1818,6 +1858,9 @@ __device__ __forceinline__ int fill_class(const ImageDesc &im) {
   if (im.ch[0] == 1 && im.cv[0] == 1 && im.ch[1] == 1 && im.cv[1] == 1 && im.ch[2] == 1 && im.cv[2] == 1 &&
       im.crec == 0)
     return z ? FC_444_Z : FC_444;
+  if (im.ch[0] == 1 && im.cv[0] == 2 && im.ch[1] == 1 && im.cv[1] == 1 && im.ch[2] == 1 && im.cv[2] == 1 &&
+      im.crec == 0)
+    return z ? FC_440_Z : FC_440;  // no box-filter exception: libjpeg's belongs to the h2 cases
   if (im.ch[0] != 2 || im.ch[1] != 1 || im.cv[1] != 1 || im.ch[2] != 1 || im.cv[2] != 1 || im.crec != 6u)
     return FC_GENERIC;
   if (!z && (im.cdsw[1] <= 2 || im.cdsw[2] <= 2)) return FC_GENERIC;  // libjpeg's box filter for tiny widths
@@ -1827,17 +1870,17 @@ __device__ __forceinline__ int fill_class(const ImageDesc &im) {
 }
 
 // The raw plane words one octet of a specialised fill reads: luma, and the
-// chroma (records, or plain samples for 4:4:4) of the near (0) and far (1)
-// chroma rows.  Loading them is split from the arithmetic (hcolor_fc8) so
-// the band kernel can issue the next band's loads before the convolution.
+// chroma (records, or plain samples for 4:4:4 and 4:4:0) of the near (0) and
+// far (1) chroma rows.  Loading them is split from the arithmetic (hcolor_fc8)
+// so the band kernel can issue the next band's loads before the convolution.
 struct FillRaw {
   u32x2 y, b0, r0, b1, r1;
 };
 
 template <int FC>
 __device__ __forceinline__ FillRaw hload_fc8(const ImageDesc &im, uint32_t y, uint32_t x0) {
-  constexpr bool Z = FC == FC_420_Z || FC == FC_422_Z || FC == FC_444_Z;
-  constexpr int SS = (FC == FC_420 || FC == FC_420_Z) ? 2 : (FC == FC_422 || FC == FC_422_Z) ? 1 : 0;
+  constexpr bool Z = fc_zune(FC);
+  constexpr int SS = fc_ss(FC);
   const DG_GLOBAL uint8_t *pY = gp<const uint8_t>(im.plane[0]);
   const DG_GLOBAL uint8_t *pB = gp<const uint8_t>(im.plane[1]);
   const DG_GLOBAL uint8_t *pR = gp<const uint8_t>(im.plane[2]);
@@ -1848,6 +1891,13 @@ __device__ __forceinline__ FillRaw hload_fc8(const ImageDesc &im, uint32_t y, ui
     f.b0 = *(const DG_GLOBAL u32x2 *)(pB + (size_t)__umul24(y, sC) + x0);
     f.r0 = *(const DG_GLOBAL u32x2 *)(pR + (size_t)__umul24(y, sC) + x0);
     f.b1 = f.r1 = u32x2{0, 0};
+  } else if (SS == 3) {  // the near and the far chroma row, clamped as upsample8 / upsample8_zune clamp them
+    const uint32_t rr = y >> 1, last = Z ? im.cbh[1] * 8 - 1 : im.cdsh[1] - 1;
+    const uint32_t rn = (y & 1) ? (rr + 1 <= last ? rr + 1 : last) : (rr > 0 ? rr - 1 : 0);
+    f.b0 = *(const DG_GLOBAL u32x2 *)(pB + (size_t)__umul24(rr, sC) + x0);
+    f.r0 = *(const DG_GLOBAL u32x2 *)(pR + (size_t)__umul24(rr, sC) + x0);
+    f.b1 = *(const DG_GLOBAL u32x2 *)(pB + (size_t)__umul24(rn, sC) + x0);
+    f.r1 = *(const DG_GLOBAL u32x2 *)(pR + (size_t)__umul24(rn, sC) + x0);
   } else {
     const uint32_t c0 = x0 >> 1;
     uint32_t rr = y, rn = y;
@@ -1869,9 +1919,10 @@ __device__ __forceinline__ FillRaw hload_fc8(const ImageDesc &im, uint32_t y, ui
 }
 
 template <int FC>
-__device__ __forceinline__ void hcolor_fc8(const ImageDesc &im, const FillRaw &f, uint32_t x0, uint32_t v[8]) {
-  constexpr bool Z = FC == FC_420_Z || FC == FC_422_Z || FC == FC_444_Z;
-  constexpr int SS = (FC == FC_420 || FC == FC_420_Z) ? 2 : (FC == FC_422 || FC == FC_422_Z) ? 1 : 0;
+__device__ __forceinline__ void hcolor_fc8(const ImageDesc &im, const FillRaw &f, uint32_t x0, uint32_t y,
+                                           uint32_t v[8]) {
+  constexpr bool Z = fc_zune(FC);
+  constexpr int SS = fc_ss(FC);
   int32_t Yv[8], Cb[8], Cr[8];
   auto unpack8 = [](u32x2 w, int32_t o[8]) {
 #pragma unroll
@@ -1890,6 +1941,22 @@ __device__ __forceinline__ void hcolor_fc8(const ImageDesc &im, const FillRaw &f
   if (SS == 0) {
     unpack8(f.b0, Cb);
     unpack8(f.r0, Cr);
+  } else if (SS == 3) {
+    // vertical only, on u16 pairs (few live registers: the 32-tap kernel has none to spare):
+    // libjpeg h1v2 fancy (3 near + far + 1 on even rows, + 2 on odd) / zune (+ 2), >> 2
+    const uint32_t bias = Z ? 0x00020002u : (y & 1) ? 0x00020002u : 0x00010001u;
+    auto blend = [&](u32x2 nr, u32x2 fa, int32_t o[8]) {
+#pragma unroll
+      for (int i = 0; i < 4; i++) {  // bytes (i, i + 4) of the octet; every sum is below 2^16
+        const uint32_t sel = 0x0C040C00u + 0x00010001u * (uint32_t)i;
+        const uint32_t n2 = __builtin_amdgcn_perm(nr.y, nr.x, sel), f2 = __builtin_amdgcn_perm(fa.y, fa.x, sel);
+        const uint32_t w = (3u * n2 + f2 + bias) >> 2;
+        o[i] = (int32_t)(w & 0xFFu);
+        o[i + 4] = (int32_t)((w >> 16) & 0xFFu);
+      }
+    };
+    blend(f.b0, f.b1, Cb);
+    blend(f.r0, f.r1, Cr);
   } else {
     const uint32_t sC = im.cbw[1] * 8, c0 = x0 >> 1;
     int32_t b[6], r[6];
@@ -2067,7 +2134,7 @@ __device__ __forceinline__ T bcast(S v) {
 }
 
 // One octet of a zune fill (hcolor_fc8<FC_4xx_Z>'s arithmetic; SS = 2
-// 4:2:0, 1 4:2:2, 0 4:4:4) as u16 pairs per channel: R[i] = (pixel 2i,
+// 4:2:0, 1 4:2:2, 0 4:4:4, 3 4:4:0) as u16 pairs per channel: R[i] = (pixel 2i,
 // pixel 2i + 1) of the octet.
 template <int SS>
 __device__ __forceinline__ void hpl_zune(const ImageDesc &im, const FillRaw &f, uint32_t x0, uint32_t R[4],
@@ -2080,6 +2147,19 @@ __device__ __forceinline__ void hpl_zune(const ImageDesc &im, const FillRaw &f, 
 #pragma unroll
       for (int i = 0; i < 4; i++)
         Cp[pl][i] = bcast<u16x2>(__builtin_amdgcn_perm(0u, i < 2 ? w.x : w.y, (i & 1) ? 0x0C030C02u : 0x0C010C00u));
+    }
+  } else if (SS == 3) {  // full-rate columns, vertical blend only: (3 near + far + 2) >> 2
+    const u16x2 two = {2, 2}, three = {3, 3};
+#pragma unroll
+    for (int pl = 0; pl < 2; pl++) {
+      const u32x2 w = pl ? f.r0 : f.b0, fw = pl ? f.r1 : f.b1;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const uint32_t sel = (i & 1) ? 0x0C030C02u : 0x0C010C00u;
+        const u16x2 nr = bcast<u16x2>(__builtin_amdgcn_perm(0u, i < 2 ? w.x : w.y, sel));
+        const u16x2 fa = bcast<u16x2>(__builtin_amdgcn_perm(0u, i < 2 ? fw.x : fw.y, sel));
+        Cp[pl][i] = (nr * three + fa + two) >> 2;
+      }
     }
   } else {
     // the 6 samples of a chroma record (load_crec6's order: left neighbour,
@@ -2262,12 +2342,12 @@ __device__ __forceinline__ void hband(const ImageDesc &im, const ResizePass &ps,
           // a thread's first job of the band was loaded before the previous
           // band's convolution (pre); later ones load here
           const FillRaw f = (PREFETCH && j == t) ? pre : hload_fc8<FC>(im, ps.row0 + y0 + r, p0 + 8 * q);
-          if (FC == FC_420_Z || FC == FC_422_Z || FC == FC_444_Z) {
+          if (fc_zune(FC)) {
             uint32_t Rw[4], Gw[4], Bw[4];  // the planar kernel's packed zune fill, back to pixel dwords
-            hpl_zune<FC == FC_420_Z ? 2 : FC == FC_422_Z ? 1 : 0>(im, f, p0 + 8 * q, Rw, Gw, Bw);
+            hpl_zune<fc_ss(FC)>(im, f, p0 + 8 * q, Rw, Gw, Bw);
             hpl_join(Rw, Gw, Bw, v);
           } else {
-            hcolor_fc8<FC>(im, f, p0 + 8 * q, v);
+            hcolor_fc8<FC>(im, f, p0 + 8 * q, ps.row0 + y0 + r, v);
           }
         }
         hput8(v, seg + r * SS + 8 * q);
@@ -2339,6 +2419,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX == 8 ?
       case FC_422_Z: hband<KMAX, FUSED, FC_422_Z, PF>(im, ps, it.item0, seg, ob, ext); return;
       case FC_444: hband<KMAX, FUSED, FC_444, PF>(im, ps, it.item0, seg, ob, ext); return;
       case FC_444_Z: hband<KMAX, FUSED, FC_444_Z, PF>(im, ps, it.item0, seg, ob, ext); return;
+      case FC_440: hband<KMAX, FUSED, FC_440, PF>(im, ps, it.item0, seg, ob, ext); return;
+      case FC_440_Z: hband<KMAX, FUSED, FC_440_Z, PF>(im, ps, it.item0, seg, ob, ext); return;
       default: break;
     }
   }
@@ -2472,11 +2554,11 @@ __device__ __forceinline__ void hband_pl(const ImageDesc &im, const ResizePass &
         hpl_split(v, Rw, Gw, Bw);
       } else {
         const FillRaw f = (PREFETCH && j == t) ? pre : hload_fc8<FC>(im, ps.row0 + y0 + r, p0 + 8 * q);
-        if (FC == FC_420_Z || FC == FC_422_Z || FC == FC_444_Z) {
-          hpl_zune<FC == FC_420_Z ? 2 : FC == FC_422_Z ? 1 : 0>(im, f, p0 + 8 * q, Rw, Gw, Bw);
+        if (fc_zune(FC)) {
+          hpl_zune<fc_ss(FC)>(im, f, p0 + 8 * q, Rw, Gw, Bw);
         } else {
           uint32_t v[8];
-          hcolor_fc8<FC>(im, f, p0 + 8 * q, v);
+          hcolor_fc8<FC>(im, f, p0 + 8 * q, ps.row0 + y0 + r, v);
           hpl_split(v, Rw, Gw, Bw);
         }
       }
@@ -2536,6 +2618,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX == 8 |
       case FC_420_Z: hband_pl<KMAX, FC_420_Z, PF>(im, ps, it.item0, segp, ob, ext); return;
       case FC_422_Z: hband_pl<KMAX, FC_422_Z, PF>(im, ps, it.item0, segp, ob, ext); return;
       case FC_444_Z: hband_pl<KMAX, FC_444_Z, PF>(im, ps, it.item0, segp, ob, ext); return;
+      case FC_440_Z: hband_pl<KMAX, FC_440_Z, PF>(im, ps, it.item0, segp, ob, ext); return;
       default: break;
     }
   } else {
@@ -2543,6 +2626,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KMAX == 8 |
       case FC_420: hband_pl<KMAX, FC_420, PF>(im, ps, it.item0, segp, ob, ext); return;
       case FC_422: hband_pl<KMAX, FC_422, PF>(im, ps, it.item0, segp, ob, ext); return;
       case FC_444: hband_pl<KMAX, FC_444, PF>(im, ps, it.item0, segp, ob, ext); return;
+      case FC_440: hband_pl<KMAX, FC_440, PF>(im, ps, it.item0, segp, ob, ext); return;
       default: break;
     }
   }

@@ -256,6 +256,20 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 DG_ERR_UNSUPPORTED those failures return)
  *   "progressive" 1 = decode progressive JPEGs on the GPU (default 1; 0: DG_ERR_UNSUPPORTED, the
  *                 caller's CPU decoder takes them)
+ *   "jpeg_h1v2"   1 = decode colour JPEGs with a component at the full horizontal and half the vertical
+ *                 rate (4:4:0: Y 1x2, Cb / Cr 1x1 -- what a lossless 90-degree rotation makes of a 4:2:2
+ *                 file -- and mixed layouts with such a component), baseline and progressive.  Default 0:
+ *                 DG_ERR_UNSUPPORTED ("chroma sampling other than 4:4:4/4:2:2/4:2:0"), as dg_probe's
+ *                 gpu_supported reports, which describes the default options.  With 1 a 3-component
+ *                 frame is accepted when every component's ratio to the largest factors is 1x1, 2x1,
+ *                 2x2 or 1x2 (at most 10 blocks per MCU, as before; 4:1:1 stays unsupported).  Output
+ *                 row y of such a component blends plane row r = y >> 1 with the row above (even y) or
+ *                 below (odd y).  decode_semantics 0, libjpeg-turbo's h1v2_fancy_upsample (bit-exact
+ *                 with Pillow): (3 * near + far + bias) >> 2, bias 1 on even and 2 on odd rows, the far
+ *                 row clamped to the component's rows, no box filter for narrow images.
+ *                 decode_semantics 1, zune-jpeg's upsample_vertical: (3 * near + far + 2) >> 2 on both
+ *                 phases, the far row clamped to the MCU-padded rows (recalled from the crate's source
+ *                 and parity-unpinned, like the rest of that mode).  Any other value: DG_ERR_INVALID
  *   "png16"       1 = decode 16-bit PNGs on the GPU (default 0: DG_ERR_UNSUPPORTED, as dg_probe's
  *                 gpu_supported reports, which describes the default options).  Colour types 0/2/4/6
  *                 become Luma16 / Rgb16 / LumaA16 / Rgba16 (a tRNS key adds a 16-bit alpha, 0 or
