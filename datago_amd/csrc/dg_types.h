@@ -39,7 +39,8 @@ constexpr int kLutBits = 10;          // Huffman first-level lookup width
 constexpr int kMaxSlots = 6;         // Huffman tables per image (DC/AC x 3 components)
 constexpr int kSubPerWg = 256;       // entropy subsequences per workgroup (= threads)
 constexpr int kDefaultSubBits = 2048; // destuffed bits per subsequence
-constexpr int kDestuffChunk = 4096;   // raw bytes per destuff workgroup (256 x 16)
+constexpr int kDestuffChunk = 4096;   // raw bytes per destuff chunk (one wave of k_destuff_count / _write)
+constexpr uint32_t kDsWgChunks = 4;   // consecutive chunks per workgroup of k_destuff_count / _write
 constexpr uint32_t kInf = 0xFFFFFFFFu;
 
 // Canonical Huffman table for the GPU decoder (built on the host, pooled).

@@ -1782,9 +1782,9 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
       HIPCHK(hipMemsetAsync(dst, 0, (size_t)(b.ds_n + 1) * 8, sl.st));
       launch_destuff_one(sl.st, dm, lst(L_DESTUFF), cnt(L_DESTUFF), dst);
     } else {
-      launch_destuff_count(sl.st, dd, lst(L_DESTUFF), cnt(L_DESTUFF));
+      launch_destuff_count(sl.st, dd, lst(L_DESTUFF_WG), cnt(L_DESTUFF_WG));
       launch_destuff_scan(sl.st, dm, lst(L_SCAN), cnt(L_SCAN));
-      launch_destuff_write(sl.st, dd, lst(L_DESTUFF), cnt(L_DESTUFF));
+      launch_destuff_write(sl.st, dd, lst(L_DESTUFF_WG), cnt(L_DESTUFF_WG));
     }
   }
   if (next()) return DG_ERR_DEVICE;

@@ -189,6 +189,7 @@ enum ListId {
   L_EXPAND16,                                               // 16-bit PNG sample step (k_png_expand16)
   L_R16T, L_R16V, L_R16H,                                   // 16-bit resize: tap tables, V pass, H pass (dg_resize16.hip)
   L_PENC_ROW16,                                             // PNG re-encode of 16-bit samples: filter rows (k_penc_filter16)
+  L_DESTUFF_WG,                                             // every kDsWgChunks-th destuff chunk (k_destuff_count / _write)
   L_COUNT
 };
 static_assert((int)L_COUNT <= 48, "Batch::lists");

@@ -1349,6 +1349,7 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
       for (uint32_t w = 0; w < d.nsub; w += kSubPerWg - 1) b.lists[L_SYNC].push_back({I, w});
       b.descs[di].ds_state0 = (uint32_t)b.lists[L_DESTUFF].size();  // k_destuff_one's state words, list order
       for (uint32_t c = 0; c < d.nchunk; c++) b.lists[L_DESTUFF].push_back({I, c});
+      for (uint32_t c = 0; c < d.nchunk; c += kDsWgChunks) b.lists[L_DESTUFF_WG].push_back({I, c});
       b.lists[L_SCAN].push_back({I, 0});
     }
     uint32_t items = 0;

@@ -18,6 +18,7 @@
 // LDS-resident Huffman tables and coefficient blocks, coalesced row stores.
 #include <hip/hip_runtime.h>
 
+#include "dg_destuff.h"
 #include "dg_entropy.h"
 #include "dg_pixel.h"
 #include "dg_plane.h"
@@ -38,13 +39,24 @@ __device__ __forceinline__ void load_tables(HuffTable *tabs, const HuffTable *po
   }
 }
 
+// Blocks b and b+8 land on the same XCD (round-robin placement, speed only):
+// map them to consecutive work items so each XCD's L2 sees a contiguous run
+// of rows of one image instead of every eighth row of all of them.
+__device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t n) {
+  const uint32_t per = n >> 3, rem = n & 7, x = b & 7, l = b >> 3;
+  return x * per + (x < rem ? x : rem) + l;
+}
+
 // ------------------------------------------------------------ destuffing
 // Raw scan -> destuffed stream + RST marker positions, in three passes over
-// 4 KiB raw chunks (count / per-image scan / write).  Each thread owns 16 raw
-// bytes, read with six aligned dword loads that also cover its neighbours;
-// chunks of 16 with no 0xFF byte (all but a few percent of them) are kept
-// whole without per-byte work.  The write pass stages the chunk's kept bytes
-// in LDS and stores them with aligned dwords.
+// 4 KiB raw chunks (count / per-image scan / write).  In the count and write
+// passes a wave owns a chunk and a lane 64 raw bytes of it, classified four
+// bytes at a time without branches (dg_destuff.h: a wave of 64 lanes meets an
+// 0xFF byte in nearly every group of 16 bytes, so work behind a per-group
+// test is done by every wave anyway).  The write pass stages the kept bytes
+// of four chunks in LDS and stores them in runs along the interleaved rows.
+// The one-pass form (k_destuff_one) keeps a thread per 16 raw bytes, read
+// with six aligned dword loads that also cover its neighbours (destuff16).
 
 struct Destuff16 {
   uint32_t kept, mks;  // kept bytes, RST markers among the 16
@@ -121,27 +133,76 @@ __device__ __forceinline__ Destuff16 destuff16(const DG_GLOBAL uint8_t *raw, uin
   return d;
 }
 
+// One lane's 64 raw bytes from byte i0 of the scan, with the bytes before and
+// after them.  The window loads are dword-aligned and lie wholly inside the
+// scan, wherever the scan lies in the caller's buffer; the spans at the head
+// and the tail of the scan, where they would not, take byte loads.
+typedef u32x4 u32x4_dw __attribute__((aligned(4)));
+typedef u32x2 u32x2_dw __attribute__((aligned(4)));
+__device__ __forceinline__ uint32_t ds_load_span(const DG_GLOBAL uint8_t *raw, uint32_t n, uint32_t i0,
+                                                 uint32_t r[16], uint32_t *prev, uint32_t *next) {
+  const uint32_t nv = i0 < n ? (n - i0 < kDsLane ? n - i0 : kDsLane) : 0u;
+  if (ds_window_in_scan(i0, n)) {
+    // bytes [i0 - 1, i0 + 65) lie in the 72 bytes from a0 >= raw + i0 - 4
+    const uintptr_t a0 = (uintptr_t)(raw + i0 - 1) & ~(uintptr_t)3;
+    const uint32_t sh = (uint32_t)((uintptr_t)(raw + i0 - 1) & 3);
+    uint32_t x[18];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const u32x4 v = *(const DG_GLOBAL u32x4_dw *)(a0 + 16 * k);
+      x[4 * k] = v.x;
+      x[4 * k + 1] = v.y;
+      x[4 * k + 2] = v.z;
+      x[4 * k + 3] = v.w;
+    }
+    const u32x2 v = *(const DG_GLOBAL u32x2_dw *)(a0 + 64);
+    x[16] = v.x;
+    x[17] = v.y;
+    ds_window(x, sh, r, prev, next);
+  } else if (nv) {
+    ds_span_bytes(raw + i0, nv, i0 > 0u, i0 + kDsLane < n, r, prev, next);
+  } else {
+#pragma unroll
+    for (int m = 0; m < 16; m++) r[m] = 0u;
+    *prev = 0u;
+  }
+  if (i0 + kDsLane >= n) *next = 0xD9u;
+  return nv;
+}
+
+// Count pass: a wave counts one chunk, a workgroup kDsWgChunks consecutive
+// chunks of one image (the list names every kDsWgChunks-th chunk).
 __global__ __launch_bounds__(256) void k_destuff_count(const ImageDesc *__restrict__ imgs,
                                                        const WgItem *__restrict__ list) {
-  __shared__ uint32_t rk[256], rm[256];
   const WgItem it = list[blockIdx.x];
   const ImageDesc &im = imgs[it.image];
-  const int t = threadIdx.x;
-  const Destuff16 d = destuff16(gp<const uint8_t>(im.scan), im.scan_len, it.item0 * kDestuffChunk + t * 16);
-  rk[t] = d.kept;
-  rm[t] = d.mks;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) {
-      rk[t] += rk[t + off];
-      rm[t] += rm[t + off];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t c = it.item0 + wave;
+  if (c >= im.nchunk) return;  // wave-uniform
+  uint32_t r[16], prev, next;
+  const uint32_t nv =
+      ds_load_span(gp<const uint8_t>(im.scan), im.scan_len, c * kDestuffChunk + lane * kDsLane, r, &prev, &next);
+  uint32_t v;  // kept bytes | markers << 16: <= 4096 kept, <= 2048 markers per chunk
+  if (nv == kDsLane) {
+    uint32_t K[16];
+    const uint32_t any = ds_keep_flags64(r, prev, next, K);
+    v = ds_count_flags64(K);
+    if (any) {
+      uint32_t M[16];
+      ds_marker_flags64(r, next, M);
+      v |= ds_count_flags64(M) << 16;
     }
-    __syncthreads();
+  } else {  // the scan's last bytes
+    uint64_t km, mm;
+    ds_classify64(r, prev, next, nv, &km, &mm);
+    v = ds_popc64(km) | (ds_popc64(mm) << 16);
   }
-  if (t == 0) {
-    DG_GLOBAL uint32_t *ch = gp<uint32_t>(im.chunk) + it.item0 * 4;
-    ch[0] = rk[0];
-    ch[1] = rm[0];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if (lane == 0) {
+    DG_GLOBAL uint32_t *ch = gp<uint32_t>(im.chunk) + c * 4;
+    ch[0] = v & 0xFFFFu;
+    ch[1] = v >> 16;
   }
 }
 
@@ -185,65 +246,114 @@ __global__ __launch_bounds__(256) void k_destuff_scan(ImageDesc *__restrict__ im
   }
 }
 
+// Write pass: each wave compacts its chunk into the workgroup's staging
+// buffer at the place the chunk offsets of k_destuff_scan give it (no wave
+// waits for another), then the workgroup stores its 16 KiB of output.  In the
+// interleaved layout, word j of 64 consecutive subsequences is one 256-byte
+// row, and 16 KiB are 64 subsequences of the default size: a wave stores
+// word j of 64 consecutive subsequences at a time, which is a run of
+// (64 - c) * 4 bytes in one tile's row and of c * 4 in the next tile's,
+// instead of 64 dwords in 64 rows.  The workgroups before and after this one
+// fill the rest of those rows; the list is walked so that they run on the
+// same XCD, whose L2 then holds the whole line.  What is left over after the
+// groups of 64 (one subsequence, usually) goes out word by word.
 __global__ __launch_bounds__(256) void k_destuff_write(const ImageDesc *__restrict__ imgs,
                                                        const WgItem *__restrict__ list) {
-  __shared__ uint32_t sk[256], sm[256];
-  __shared__ uint8_t buf[kDestuffChunk];
-  const WgItem it = list[blockIdx.x];
+  __shared__ uint32_t st[kDsStageAlloc];
+  const WgItem it = list[xcd_remap(blockIdx.x, gridDim.x)];
   const ImageDesc &im = imgs[it.image];
-  const int t = threadIdx.x;
-  const Destuff16 d = destuff16(gp<const uint8_t>(im.scan), im.scan_len, it.item0 * kDestuffChunk + t * 16);
-  sk[t] = d.kept;
-  sm[t] = d.mks;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {
-    uint32_t a = t >= off ? sk[t - off] : 0u, b = t >= off ? sm[t - off] : 0u;
-    __syncthreads();
-    sk[t] += a;
-    sm[t] += b;
-    __syncthreads();
-  }
-  const DG_GLOBAL uint32_t *ch = gp<const uint32_t>(im.chunk) + it.item0 * 4;
-  const uint32_t O = ch[2];           // chunk's first output byte
-  uint32_t o = sk[t] - d.kept;        // this thread's first byte within the chunk
-  const uint32_t total = sk[255];
-  if (d.km == 0xFFFFu) {
-#pragma unroll
-    for (uint32_t j = 0; j < 16; j++) buf[o + j] = (uint8_t)(d.r[j >> 2] >> (8 * (j & 3)));
-  } else {
-    uint32_t mo = ch[3] + sm[t] - d.mks;
-    DG_GLOBAL uint32_t *mk = gp<uint32_t>(im.mk);
-    for (uint32_t j = 0; j < 16; j++) {
-      if ((d.mm >> j) & 1u) {
-        if (mo < im.mk_cap) mk[mo] = (O + o) * 8;
-        mo++;
+  const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+  const uint32_t c0 = it.item0;
+  const uint32_t nc = im.nchunk - c0 < kDsWgChunks ? im.nchunk - c0 : kDsWgChunks;
+  const DG_GLOBAL uint32_t *ch = gp<const uint32_t>(im.chunk) + c0 * 4;
+  const uint32_t O = ch[2];                                    // the workgroup's first output byte
+  const uint32_t E = ch[(nc - 1) * 4 + 2] + ch[(nc - 1) * 4];  // one past its last
+  const uint32_t wbase = O >> 2;                               // logical word of staging dword 0
+  if (wave < nc) {
+    uint32_t r[16], prev, next;
+    const uint32_t nv = ds_load_span(gp<const uint8_t>(im.scan), im.scan_len,
+                                     (c0 + wave) * kDestuffChunk + lane * kDsLane, r, &prev, &next);
+    uint32_t K[16], any = 0, own;
+    uint64_t km = 0, mm = 0;
+    if (nv == kDsLane) {
+      any = ds_keep_flags64(r, prev, next, K);
+      own = ds_count_flags64(K);
+      if (any) {
+        uint32_t M[16];
+        ds_marker_flags64(r, next, M);
+        own |= ds_count_flags64(M) << 16;
       }
-      if ((d.km >> j) & 1u) buf[o++] = (uint8_t)(d.r[j >> 2] >> (8 * (j & 3)));
+    } else {  // the scan's last bytes
+      ds_classify64(r, prev, next, nv, &km, &mm);
+      own = ds_popc64(km) | (ds_popc64(mm) << 16);
+    }
+    uint32_t v = own;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t u = __shfl_up(v, o);
+      if (lane >= (uint32_t)o) v += u;
+    }
+    const uint32_t ex = v - own;  // kept bytes | markers << 16 of the lanes before
+    const uint32_t pos = ch[wave * 4 + 2] - 4u * wbase + (ex & 0xFFFFu);
+    // (the counts are this kernel's own and the offsets k_destuff_count's: a
+    // scan that changed in between must not write past the buffer)
+    if (pos + (own & 0xFFFFu) <= 4u * kDsStageWords) {
+      uint32_t mo = ch[wave * 4 + 3] + (ex >> 16);
+      DG_GLOBAL uint32_t *mk = gp<uint32_t>(im.mk);
+      const uint32_t cap = im.mk_cap;
+      auto mark = [&](uint32_t p) {
+        if (mo < cap) mk[mo] = (4u * wbase + p) * 8u;
+        mo++;
+      };
+      if (nv == kDsLane) {
+        if (own >> 16) {
+          uint32_t M[16];
+          ds_marker_flags64(r, next, M);
+          ds_mark64(pos, K, M, mark);
+        }
+        if ((own & 0xFFFFu) != kDsLane) ds_compact64(r, K);
+        ds_put_bytes(st, pos, r, own & 0xFFFFu);
+      } else {
+        ds_emit64(st, pos, r, km, mm, mark);
+      }
     }
   }
   __syncthreads();
-  // buf[0, total) -> logical bytes [O, O + total) of the interleaved stream:
-  // partial words at both ends byte by byte, whole words as dword stores
   DG_GLOBAL uint8_t *ds = gp<uint8_t>(im.ds);
   DG_GLOBAL uint32_t *ds4 = (DG_GLOBAL uint32_t *)ds;
   const uint32_t lsw = im.ds_lsw;
-  const uint32_t mis = (4u - (O & 3u)) & 3u;  // bytes to the next word boundary
-  const uint32_t head = mis < total ? mis : total;
-  const uint32_t nd = (total - head) >> 2;
-  if ((uint32_t)t < head) {
+  // partial words at both ends byte by byte (their other bytes are a neighbour's)
+  const uint32_t wA = (O + 3u) >> 2, wB = E >> 2;  // whole logical words [wA, wB)
+  const uint32_t head_end = E < wA * 4u ? E : wA * 4u;
+  if (t < head_end - O) {
     const uint32_t q = O + t;
-    ds[(size_t)ds_word_index(q >> 2, lsw) * 4 + (q & 3)] = buf[t];
+    ds[(size_t)ds_word_index(q >> 2, lsw) * 4 + (q & 3u)] = (uint8_t)ds_get_byte(st, q - 4u * wbase);
   }
-  const uint32_t w0 = (O + head) >> 2;  // first whole logical word
-  for (uint32_t q = t; q < nd; q += 256) {
-    const uint32_t b0 = head + 4 * q;
-    ds4[ds_word_index(w0 + q, lsw)] = (uint32_t)buf[b0] | ((uint32_t)buf[b0 + 1] << 8) |
-                                      ((uint32_t)buf[b0 + 2] << 16) | ((uint32_t)buf[b0 + 3] << 24);
+  const uint32_t tail0 = wB * 4u > head_end ? wB * 4u : head_end;
+  if (t < E - tail0) {
+    const uint32_t q = tail0 + t;
+    ds[(size_t)ds_word_index(q >> 2, lsw) * 4 + (q & 3u)] = (uint8_t)ds_get_byte(st, q - 4u * wbase);
   }
-  const uint32_t tail0 = head + 4 * nd;
-  if ((uint32_t)t < total - tail0) {
-    const uint32_t q = O + tail0 + t;
-    ds[(size_t)ds_word_index(q >> 2, lsw) * 4 + (q & 3)] = buf[tail0 + t];
+  if (wB <= wA) return;
+  const uint32_t R1 = (1u << lsw) - 1u;
+  const uint32_t sA = wA >> lsw, ns = ((wB - 1u) >> lsw) - sA + 1u;
+  const uint32_t nfull = ns & ~63u, rem = ns & 63u;
+  for (uint32_t idx = t; idx < nfull << lsw; idx += 256) {  // rows of 64 subsequences
+    const uint32_t s = sA + ((idx >> (6u + lsw)) << 6) + (idx & 63u), j = (idx >> 6) & R1;
+    const uint32_t w = (s << lsw) + j;
+    if (w >= wA && w < wB) ds4[ds_word_index(w, lsw)] = st[ds_pad(w - wbase)];
+  }
+  const uint32_t sR = sA + nfull;
+  if (rem >= 16u) {  // rows of the rem subsequences left
+    for (uint32_t idx = t; idx < 64u << lsw; idx += 256) {
+      const uint32_t w = ((sR + (idx & 63u)) << lsw) + (idx >> 6);
+      if ((idx & 63u) < rem && w >= wA && w < wB) ds4[ds_word_index(w, lsw)] = st[ds_pad(w - wbase)];
+    }
+  } else {  // word by word
+    for (uint32_t idx = t; idx < rem << lsw; idx += 256) {
+      const uint32_t w = (sR << lsw) + idx;
+      if (w >= wA && w < wB) ds4[ds_word_index(w, lsw)] = st[ds_pad(w - wbase)];
+    }
   }
 }
 
@@ -1786,14 +1896,6 @@ __global__ __launch_bounds__(256) void k_resize_h(const ImageDesc *__restrict__ 
       hconv(srow, (uint32_t)bounds[2 * x] * C, bounds[2 * x + 1], coef + (size_t)x * ps.ksize, C,
             prec, drow + (size_t)x * C);
   }
-}
-
-// Blocks b and b+8 land on the same XCD (round-robin placement, speed only):
-// map them to consecutive work items so each XCD's L2 sees a contiguous run
-// of rows of one image instead of every eighth row of all of them.
-__device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t n) {
-  const uint32_t per = n >> 3, rem = n & 7, x = b & 7, l = b >> 3;
-  return x * per + (x < rem ? x : rem) + l;
 }
 
 // ---- band H pass
