@@ -260,10 +260,19 @@ DG_HD void multi_chain(const uint16_t *mt, uint32_t mi, uint32_t bits, uint32_t 
 }
 
 // Accumulators of one subsequence decode.
-struct RangeAcc {
+// NC: components the pass keeps DC sums for -- 3, or 4 in the instantiations
+// a batch with a four-component image runs (option "jpeg_cmyk").
+template <int NC>
+struct RangeAccN {
   uint32_t out;
   uint32_t m, n;
-  int32_t dc[3];
+  int32_t dc[NC];
+};
+using RangeAcc = RangeAccN<3>;
+// a parameter type that takes no part in template argument deduction
+template <class T>
+struct NoDeduce {
+  typedef T type;
 };
 
 // Write-side context: coefficient block buffer of this thread (64 int16,
@@ -274,12 +283,11 @@ struct RangeAcc {
 // cover all 64 banks (the unswizzled 128-byte stride put them on two groups
 // of four).  72-int16 buffers did the same with 12% more LDS; at 64 the
 // kernel fits three workgroups per CU instead of two.
-struct WriteCtx {
+struct WriteCtxBase {
   int16_t *blk;
   uint32_t sw = 0;  // swizzle of this thread's buffer (int16 units; 0 on the host)
   DG_GLOBAL int16_t *coef;
   uint32_t seg, nin;
-  int32_t pred[3];
   uint32_t blocks_per_seg, total_blocks;
   int32_t cur;   // global index of the block being filled (-1 = none / dropped)
   uint32_t zs;   // first zigzag index this thread owns in the current block
@@ -300,14 +308,20 @@ struct WriteCtx {
   uint32_t img;             // descriptor index
 #endif
 };
+// ... and the DC predictors of its NC components
+template <int NC>
+struct WriteCtxN : WriteCtxBase {
+  int32_t pred[NC];
+};
+using WriteCtx = WriteCtxN<3>;
 
-DG_HD int32_t wc_index(const WriteCtx &w, uint32_t in_seg) {
+DG_HD int32_t wc_index(const WriteCtxBase &w, uint32_t in_seg) {
   if (w.blocks_per_seg && in_seg >= w.blocks_per_seg) return -1;
   uint64_t g = (uint64_t)(w.blocks_per_seg ? w.seg : 0) * w.blocks_per_seg + in_seg;
   return g < w.total_blocks ? (int32_t)g : -1;
 }
 
-DG_HD void wc_begin(WriteCtx &w, int32_t idx, uint32_t zs) {
+DG_HD void wc_begin(WriteCtxBase &w, int32_t idx, uint32_t zs) {
   w.cur = idx;
   w.zs = zs;
 #if defined(DG_DEVICE)
@@ -320,7 +334,7 @@ DG_HD void wc_begin(WriteCtx &w, int32_t idx, uint32_t zs) {
 #endif
 }
 
-DG_HD void wc_flush(WriteCtx &w, uint32_t ze) {
+DG_HD void wc_flush(WriteCtxBase &w, uint32_t ze) {
   if (w.cur < 0) return;
   DG_GLOBAL int16_t *dst = w.coef + (size_t)w.cur * 64;
   if (w.zs == 0 && ze == 64) {
@@ -346,7 +360,7 @@ DG_HD void wc_flush(WriteCtx &w, uint32_t ze) {
 #if defined(DG_DEVICE)
 // Fused IDCT: a block whose coefficients reach the coefficient buffer (not
 // IDCT-ed in the flush) is listed for k_idct_list.
-__device__ __forceinline__ void wc_list_late(WriteCtx &w, int32_t idx) {
+__device__ __forceinline__ void wc_list_late(WriteCtxBase &w, int32_t idx) {
   if (!w.im || idx < 0) return;
   const uint32_t e = atomicAdd(&w.flags->idct_late, 1u);
   if (e < w.flags->idct_cap) {
@@ -364,7 +378,7 @@ __device__ __forceinline__ void wc_list_late(WriteCtx &w, int32_t idx) {
 // global stores and 8 LDS stores whenever any lane of the wave ends a block,
 // which with ~8 symbols per block is nearly every step.  Blocks are zero
 // whenever a lane has none open, so a block start only sets its index.
-__device__ __forceinline__ void wc_coop_flush(WriteCtx &w, bool pending) {
+__device__ __forceinline__ void wc_coop_flush(WriteCtxBase &w, bool pending) {
   const uint64_t pm = __ballot(pending);
   if (!pm) return;
   const uint64_t am = __ballot(1);
@@ -454,7 +468,7 @@ __device__ __forceinline__ void wc_coop_flush(WriteCtx &w, bool pending) {
 
 // rare paths (partial blocks at range ends and restart markers): flush, then
 // restore the all-zero block
-__device__ __forceinline__ void wc_flush_zero(WriteCtx &w, uint32_t ze) {
+__device__ __forceinline__ void wc_flush_zero(WriteCtxBase &w, uint32_t ze) {
   wc_flush(w, ze);
   u32x4 *p = (u32x4 *)w.blk;
   const u32x4 zero = {0u, 0u, 0u, 0u};
@@ -466,7 +480,7 @@ __device__ __forceinline__ void wc_flush_zero(WriteCtx &w, uint32_t ze) {
 // Block flush / start inside decode_range: wave-cooperative on the device
 // when the context provides the table (COOP), per lane otherwise.
 template <bool COOP>
-DG_HD void wc_end_block(WriteCtx &w, bool &pending) {
+DG_HD void wc_end_block(WriteCtxBase &w, bool &pending) {
 #if defined(DG_DEVICE)
   if (COOP) {
     if (w.zs == 0) {
@@ -483,7 +497,7 @@ DG_HD void wc_end_block(WriteCtx &w, bool &pending) {
   wc_flush(w, 64);
 }
 template <bool COOP>
-DG_HD void wc_partial(WriteCtx &w, uint32_t ze) {
+DG_HD void wc_partial(WriteCtxBase &w, uint32_t ze) {
 #if defined(DG_DEVICE)
   if (COOP) {
     wc_flush_zero(w, ze);
@@ -560,11 +574,13 @@ constexpr uint32_t kCkptBits = 256;
 // (32, for split 16384-bit ranges: sub_auto 16384 measured no faster,
 // profiles/r04/sub16k)
 constexpr uint32_t kMaxCkpt = 16;
-struct Ckpt {
+template <int NC>
+struct CkptN {
   uint32_t st;   // packed state (rel past the checkpoint position, r, z)
   uint32_t m, n; // tail (segmented: m > 0 means the tail contains a reset)
-  int32_t dc[3];
+  int32_t dc[NC];
 };
+using Ckpt = CkptN<3>;
 
 DG_HD uint32_t num_ckpt(uint32_t sub_bits) {
   uint32_t k = (sub_bits - 1) / kCkptBits;
@@ -673,10 +689,11 @@ DG_HD uint32_t lead_in(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL uin
 //   tabs: Huffman tables indexed by slot (im.dc_slot / im.ac_slot)
 //   ck: this subsequence's checkpoint records (nullptr: none); merge: the
 //   records hold a previous decode of this range whose exit state was old_out.
-template <bool WRITE, class TAB, bool COOP = false>
+template <bool WRITE, class TAB, bool COOP = false, int NC = 3>
 DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL uint8_t *stream,
                         const DG_GLOBAL uint32_t *mk,
-                        uint32_t s, uint32_t in, RangeAcc &acc, WriteCtx *w, DG_GLOBAL Ckpt *ck = nullptr,
+                        uint32_t s, uint32_t in, RangeAccN<NC> &acc, typename NoDeduce<WriteCtxN<NC>>::type *w,
+                        DG_GLOBAL typename NoDeduce<CkptN<NC>>::type *ck = nullptr,
                         bool merge = false, uint32_t old_out = 0, StageCtx *stg = nullptr,
                         const uint16_t *mt = nullptr, uint32_t acm = 0xFFu, uint32_t pair = 0,
                         uint32_t a0o = kInf, uint32_t a1o = kInf, uint32_t chain = 0) {
@@ -690,7 +707,7 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
   uint32_t pos = a0 + st_rel(in);
   acc.m = 0;
   acc.n = 0;
-  acc.dc[0] = acc.dc[1] = acc.dc[2] = 0;
+  setn(acc.dc, 0);
   const bool stage = stg && stg->on;
   if (stage) {
     stg->n = 0;
@@ -754,11 +771,11 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
         if (owned) {
           acc.m++;
           acc.n = 0;
-          acc.dc[0] = acc.dc[1] = acc.dc[2] = 0;
+          setn(acc.dc, 0);
           if (WRITE) {
             w->seg++;
             w->nin = 0;
-            w->pred[0] = w->pred[1] = w->pred[2] = 0;
+            setn(w->pred, 0);
           }
         }
         midx++;
@@ -768,19 +785,15 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
       if (k < nck && cpos < a1 && pos >= cpos) {  // first boundary at/after checkpoint k
         uint32_t rel = pos - cpos;
         uint32_t st = pack_state(rel > 255 ? 255 : rel, r, z);
-        DG_GLOBAL Ckpt &c = ck[k];
+        DG_GLOBAL CkptN<NC> &c = ck[k];
         if (merge && c.st == st) {  // rejoined the previous decode: acc (+) tail_k
           if (c.m) {
             acc.m += c.m;
             acc.n = c.n;
-            acc.dc[0] = c.dc[0];
-            acc.dc[1] = c.dc[1];
-            acc.dc[2] = c.dc[2];
+            cpyn<NC>(acc.dc, c.dc);
           } else {
             acc.n += c.n;
-            acc.dc[0] += c.dc[0];
-            acc.dc[1] += c.dc[1];
-            acc.dc[2] += c.dc[2];
+            accn<NC>(acc.dc, c.dc);
           }
           acc.out = old_out;
           merged = true;
@@ -789,9 +802,7 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
         c.st = st;  // record the prefix for now; turned into a tail at the end
         c.m = acc.m;
         c.n = acc.n;
-        c.dc[0] = acc.dc[0];
-        c.dc[1] = acc.dc[1];
-        c.dc[2] = acc.dc[2];
+        cpyn<NC>(c.dc, acc.dc);
         k++;
         cpos += kCkptBits;
       }
@@ -822,7 +833,7 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
     pos += take_m ? mc : len + size;
     const int32_t vdc = isdc ? v : 0;
     acc.n += isdc ? 1u : 0u;
-    add3(acc.dc, comp, vdc);
+    addn(acc.dc, comp, vdc);
     if (stage) {
       if (isdc) {
         stg->started++;
@@ -832,7 +843,7 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
       }
     }
     if (WRITE) {
-      add3(w->pred, comp, vdc);
+      addn(w->pred, comp, vdc);
       if (isdc) {
         if (COOP) {
           w->cur = wc_index(*w, w->nin);
@@ -843,7 +854,7 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
         w->nin++;
       }
       const uint32_t zz = z + run;
-      if (isdc || (size && zz < 64u)) w->blk[zz ^ w->sw] = (int16_t)(isdc ? sel3(w->pred, comp) : v);
+      if (isdc || (size && zz < 64u)) w->blk[zz ^ w->sw] = (int16_t)(isdc ? seln(w->pred, comp) : v);
     }
     uint32_t zn = take_m ? zm : huff_next_z(z, sym);
     if (pair && !stage && (WRITE || !take_m)) {
@@ -896,19 +907,15 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
     acc.out = pack_state(rel > 255 ? 255 : rel, r, z);
   }
   for (uint32_t j = 0; j < k; j++) {  // prefixes written this time -> tails
-    DG_GLOBAL Ckpt &c = ck[j];
+    DG_GLOBAL CkptN<NC> &c = ck[j];
     if (acc.m > c.m) {
       c.m = acc.m - c.m;
       c.n = acc.n;
-      c.dc[0] = acc.dc[0];
-      c.dc[1] = acc.dc[1];
-      c.dc[2] = acc.dc[2];
+      cpyn<NC>(c.dc, acc.dc);
     } else {
       c.m = 0;
       c.n = acc.n - c.n;
-      c.dc[0] = acc.dc[0] - c.dc[0];
-      c.dc[1] = acc.dc[1] - c.dc[1];
-      c.dc[2] = acc.dc[2] - c.dc[2];
+      rsubn<NC>(c.dc, acc.dc);
     }
   }
 }

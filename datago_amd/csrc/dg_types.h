@@ -34,6 +34,49 @@ DG_HD void add3(int32_t v[3], uint32_t c, int32_t d) {
   v[1] += c == 1 ? d : 0;
   v[2] += c == 2 ? d : 0;
 }
+// The same for the entropy passes' component count NC (3, or 4 for a batch with a CMYK / YCCK image,
+// option "jpeg_cmyk"): c in {0..NC-1}.  NC = 3 is sel3 / add3 exactly.
+template <int NC>
+DG_HD int32_t seln(const int32_t (&v)[NC], uint32_t c) {
+  static_assert(NC == 3 || NC == 4, "three or four components");
+  if (NC == 4) return c == 0 ? v[0] : (c == 1 ? v[1] : (c == 2 ? v[2] : v[NC - 1]));
+  return c == 0 ? v[0] : (c == 1 ? v[1] : v[2]);
+}
+template <int NC>
+DG_HD void addn(int32_t (&v)[NC], uint32_t c, int32_t d) {
+  v[0] += c == 0 ? d : 0;
+  v[1] += c == 1 ? d : 0;
+  v[2] += c == 2 ? d : 0;
+  if (NC == 4) v[NC - 1] += c == 3 ? d : 0;
+}
+template <int NC>
+DG_HD void setn(int32_t (&v)[NC], int32_t x) {
+  v[0] = v[1] = v[2] = x;
+  if (NC == 4) v[NC - 1] = x;
+}
+// v = a and v += a over NC components (either side may be a record in global memory)
+template <int NC, class V, class A>
+DG_HD void cpyn(V &v, const A &a) {
+  v[0] = a[0];
+  v[1] = a[1];
+  v[2] = a[2];
+  if (NC == 4) v[NC - 1] = a[NC - 1];
+}
+template <int NC, class V, class A>
+DG_HD void accn(V &v, const A &a) {
+  v[0] += a[0];
+  v[1] += a[1];
+  v[2] += a[2];
+  if (NC == 4) v[NC - 1] += a[NC - 1];
+}
+// v = a - v: a checkpoint's prefix sums turned into its tail
+template <int NC, class V, class A>
+DG_HD void rsubn(V &v, const A &a) {
+  v[0] = a[0] - v[0];
+  v[1] = a[1] - v[1];
+  v[2] = a[2] - v[2];
+  if (NC == 4) v[NC - 1] = a[NC - 1] - v[NC - 1];
+}
 
 constexpr int kLutBits = 10;          // Huffman first-level lookup width
 constexpr int kMaxSlots = 6;         // Huffman tables per image (DC/AC x 3 components)
@@ -78,15 +121,18 @@ struct SubState {
   uint32_t out;     // state at the first symbol boundary at/after the next anchor
   uint32_t m;       // RST markers owned (FF byte inside this subsequence)
   uint32_t n;       // blocks started after the last owned marker (or the start)
-  int32_t dc[3];    // DC differences summed after the last owned marker, per component
+  int32_t dc[4];    // DC differences summed after the last owned marker, per component
   uint32_t seg;     // exclusive segmented scan: restart segment at start
   uint32_t nin;     //   blocks already started in that segment
-  int32_t dcin[3];  //   DC predictors at start
+  int32_t dcin[4];  //   DC predictors at start
   uint32_t nstart;  // decode-once staging: blocks started in the range (all segments)
   uint32_t nent;    //   staged entries
 };
+static_assert(sizeof(SubState) == 64, "SubState is one 64-byte record");
 
-enum Colorspace : uint32_t { CS_YCC = 0, CS_RGB = 1, CS_GRAY = 2 };
+// CS_CMYK / CS_YCCK: four-component Adobe files (APP14 transform 0 / 2, option "jpeg_cmyk"); k_cmyk turns their
+// planes into the RGB image
+enum Colorspace : uint32_t { CS_YCC = 0, CS_RGB = 1, CS_GRAY = 2, CS_CMYK = 3, CS_YCCK = 4 };
 
 // Resize pass along one axis (one half of a fast_image_resize `resize` call).
 struct ResizePass {
@@ -309,7 +355,7 @@ struct ImageDesc {
   uint8_t blk_comp[12];     // same, unpacked (host side / IDCT)
   uint16_t hslot[kMaxSlots];  // pool index of Huffman slot s
   uint8_t ncomp, colorspace, dec_c, nslots;  // dec_c: channels of the decoded image
-  uint16_t qpool[3];
+  uint16_t qpool[4];
   uint16_t sem;             // decode semantics: 0 libjpeg-turbo, 1 zune-jpeg (option "decode_semantics")
   uint64_t coef;            // device address of block 0 (int16 zigzag[64] per block, decode order)
   uint64_t stage;           // decode-once staging (dg_entropy.h StageCtx), 0 = off
@@ -322,12 +368,12 @@ struct ImageDesc {
   uint32_t width, height;
   uint32_t mcux, mcuy;
   uint32_t hmax, vmax;
-  uint32_t ch[3], cv[3];    // sampling factors
-  uint32_t cfirst[3];       // first block of component c within an MCU
-  uint32_t cbw[3], cbh[3];  // plane size in blocks
-  uint32_t cdsw[3], cdsh[3];// downsampled width/height (libjpeg downsampled_width)
-  uint64_t plane[3];        // device address of component planes (stride cbw*8)
-  uint64_t pix;             // decoded interleaved image (stride pix_stride), 0 for gray
+  uint32_t ch[4], cv[4];    // sampling factors
+  uint32_t cfirst[4];       // first block of component c within an MCU
+  uint32_t cbw[4], cbh[4];  // plane size in blocks
+  uint32_t cdsw[4], cdsh[4];// downsampled width/height (libjpeg downsampled_width)
+  uint64_t plane[4];        // device address of component planes (stride cbw*8)
+  uint64_t pix;             // decoded interleaved RGB image (stride pix_stride), 0 for gray
   uint32_t pix_stride;
   int32_t status;           // set by kernels on corruption
   // ---- resize plan

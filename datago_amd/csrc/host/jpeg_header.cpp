@@ -40,7 +40,7 @@ static void fail(JpegHeader &h, int st, const char *why) {
   h.why = why;
 }
 
-void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v2) {
+void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v2, bool allow_cmyk) {
   h = JpegHeader();
   if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(h, JH_CORRUPT, "not a JPEG (no SOI)");
   bool saw_sof = false;
@@ -200,7 +200,16 @@ void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v
   if (h.arithmetic) return fail(h, JH_UNSUPPORTED, "arithmetic-coded JPEG");
   if (h.lossless || (h.sof != 0xC0 && h.sof != 0xC1 && h.sof != 0xC2)) return fail(h, JH_UNSUPPORTED, "unsupported SOF type");
   if (h.precision != 8) return fail(h, JH_UNSUPPORTED, "12/16-bit JPEG");
-  if (h.ncomp != 1 && h.ncomp != 3) return fail(h, JH_UNSUPPORTED, "CMYK/2-component JPEG");
+  if (h.ncomp != 1 && h.ncomp != 3) {
+    if (!allow_cmyk) return fail(h, JH_UNSUPPORTED, "CMYK/2-component JPEG");
+    // context option jpeg_cmyk: Adobe CMYK (APP14 transform 0) and YCCK (transform 2) files
+    if (h.ncomp != 4) return fail(h, JH_UNSUPPORTED, "2-component JPEG");
+    if (!h.adobe)
+      return fail(h, JH_UNSUPPORTED, "4-component JPEG without an Adobe segment (inverted or not: ambiguous)");
+    if (h.adobe_transform == 1) return fail(h, JH_UNSUPPORTED, "4-component JPEG with Adobe transform 1 (YCbCr)");
+    if (h.adobe_transform != 0 && h.adobe_transform != 2)
+      return fail(h, JH_UNSUPPORTED, "4-component JPEG with an unknown Adobe transform");
+  }
   if (!h.progressive && h.scan_ncomp != h.ncomp) return fail(h, JH_UNSUPPORTED, "non-interleaved multi-scan JPEG");
   if (h.progressive) {
     // coefficient precision after the last scan (libjpeg coef_bits): the DC and
@@ -224,9 +233,9 @@ void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v
     if (h.comp[c].h > h.hmax) h.hmax = h.comp[c].h;
     if (h.comp[c].v > h.vmax) h.vmax = h.comp[c].v;
   }
-  if (h.ncomp == 3) {
+  if (h.ncomp >= 3) {
     int blocks = 0;
-    for (int c = 0; c < 3; c++) {
+    for (int c = 0; c < h.ncomp; c++) {
       const JpegComponent &k = h.comp[c];
       if (h.hmax % k.h || h.vmax % k.v) return fail(h, JH_UNSUPPORTED, "fractional sampling ratio");
       int hr = h.hmax / k.h, vr = h.vmax / k.v;
@@ -237,6 +246,16 @@ void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v
     }
     if (blocks > 10) return fail(h, JH_CORRUPT, "too many blocks per MCU");
   }
+  if (h.ncomp == 4 && !h.progressive) {
+    // the entropy kernels hold kMaxSlots tables per workgroup; real files name two DC and two AC tables
+    uint32_t dcs = 0, acs = 0;
+    for (int c = 0; c < 4; c++) {
+      dcs |= 1u << h.comp[c].td;
+      acs |= 1u << h.comp[c].ta;
+    }
+    if (__builtin_popcount(dcs) + __builtin_popcount(acs) > kMaxSlots)
+      return fail(h, JH_UNSUPPORTED, "more distinct Huffman tables than the decoder holds per workgroup (6)");
+  }
   for (int c = 0; c < h.ncomp; c++) {
     if (!h.qpresent[h.comp[c].tq]) return fail(h, JH_CORRUPT, "missing quantisation table");
     if (!h.progressive && (!h.dc[h.comp[c].td].present || !h.ac[h.comp[c].ta].present))
@@ -245,6 +264,8 @@ void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v
   // colour space guess (libjpeg jdapimin.c default_decompress_parms)
   if (h.ncomp == 1) {
     h.colorspace = CS_GRAY;
+  } else if (h.ncomp == 4) {
+    h.colorspace = h.adobe_transform == 0 ? CS_CMYK : CS_YCCK;
   } else if (h.jfif) {
     h.colorspace = CS_YCC;
   } else if (h.adobe) {

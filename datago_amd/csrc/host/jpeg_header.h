@@ -73,7 +73,10 @@ struct JpegHeader {
 // entropy-coded segment plus the last two bytes (EOI check).  allow_h1v2
 // (context option jpeg_h1v2) also accepts a component at the full horizontal
 // and half the vertical rate (4:4:0); without it such a file is JH_UNSUPPORTED.
-void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v2 = false);
+// allow_cmyk (context option jpeg_cmyk) also accepts four-component files with
+// an Adobe APP14 segment of transform 0 (CMYK) or 2 (YCCK); without it every
+// two- and four-component file is JH_UNSUPPORTED "CMYK/2-component JPEG".
+void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v2 = false, bool allow_cmyk = false);
 
 // Canonical Huffman code -> GPU lookup table (T.81 Annex C).  Returns false
 // for an over-subscribed code.

@@ -406,6 +406,17 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     jpeg_h1v2_ = v != 0;
     return DG_OK;
   }
+  if (k == "jpeg_cmyk") {
+    // Four-component JPEGs with an Adobe APP14 segment of transform 0 (CMYK)
+    // or 2 (YCCK) (default off: DG_ERR_UNSUPPORTED "CMYK/2-component JPEG").
+    // 1: parse_jpeg_header accepts them, the batch's entropy passes run their
+    // four-component instantiations and k_cmyk (kernels.hip) writes the RGB
+    // image that image 0.25 returns for them.  dg_probe keeps describing the
+    // default options.
+    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
+    jpeg_cmyk_ = v != 0;
+    return DG_OK;
+  }
   if (k == "resize16") {
     // 16-bit PNGs that are not their bucket's size (default off:
     // DG_ERR_UNSUPPORTED).  1, together with "png16": they resize with the
@@ -1421,7 +1432,7 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
       p.status = DG_ERR_CORRUPT;
       return DG_OK;
     }
-    parse_jpeg_header(h, len, p.hdr, jpeg_h1v2_);  // option "jpeg_h1v2"
+    parse_jpeg_header(h, len, p.hdr, jpeg_h1v2_, jpeg_cmyk_);  // options "jpeg_h1v2", "jpeg_cmyk"
     if (p.hdr.status != JH_OK) {
       p.status = p.hdr.status == JH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
       return DG_OK;
@@ -1830,16 +1841,17 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   Ckpt *ck = (Ckpt *)((char *)sl.scratch.p + sl.ckpt_off);
   if (!from_fix)
     launch_huff_sync(sl.st, dd, lst(L_SYNC), cnt(L_SYNC), hp, subs, ck, fl, b.stage_on, b.max_slots,
-                     multi_lead_ ? b.max_ac : 0u, sync_pair_, sync2_, (uint32_t)sync_chain_);
+                     multi_lead_ ? b.max_ac : 0u, sync_pair_, sync2_, (uint32_t)sync_chain_, b.nc4);
   if (next()) return DG_ERR_DEVICE;
-  launch_huff_fix(sl.st, dd, lst(L_SYNC), cnt(L_SYNC), hp, subs, ck, fl, b.stage_on, b.max_slots);
+  launch_huff_fix(sl.st, dd, lst(L_SYNC), cnt(L_SYNC), hp, subs, ck, fl, b.stage_on, b.max_slots, b.nc4);
   if (next()) return DG_ERR_DEVICE;
-  launch_huff_scan(sl.st, dm, lst(L_SCAN), cnt(L_SCAN), subs);
+  launch_huff_scan(sl.st, dm, lst(L_SCAN), cnt(L_SCAN), subs, b.nc4);
   if (next()) return DG_ERR_DEVICE;
   if (b.stage_on)
     launch_huff_scatter(sl.st, dd, lst(L_HUFF), cnt(L_HUFF), subs);
   else
-    launch_huff_write(sl.st, dm, lst(L_HUFF), cnt(L_HUFF), hp, subs, fl, b.max_slots, qp, (uint32_t)write_pair_, ck);
+    launch_huff_write(sl.st, dm, lst(L_HUFF), cnt(L_HUFF), hp, subs, fl, b.max_slots, qp, (uint32_t)write_pair_, ck,
+                      b.nc4);
   if (next()) return DG_ERR_DEVICE;
   if (next()) return DG_ERR_DEVICE;  // coeffs (side stream)
   if (pside || dc_side) HIPCHK(hipStreamWaitEvent(sl.st, sl.ev_prog, 0));  // progressive coefficients
@@ -1850,6 +1862,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     launch_idct(sl.st, dd, lst(L_IDCT), cnt(L_IDCT), qp);
   if (next()) return DG_ERR_DEVICE;
   launch_color(sl.st, dd, lst(L_COLOR), cnt(L_COLOR));
+  launch_cmyk(sl.st, dd, lst(L_CMYK), cnt(L_CMYK));
   if (next()) return DG_ERR_DEVICE;
   HIPCHK(hipStreamWaitEvent(sl.st, sl.ev_coef, 0));
   launch_alpha(sl.st, dd, lst(L_ALPHA0), cnt(L_ALPHA0), 0 | (alpha_flags << 8));

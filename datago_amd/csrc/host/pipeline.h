@@ -97,6 +97,9 @@ struct Batch {
   uint32_t v_tile = 0;     // rows per k_resize_vt tile the V lists were built for
   uint32_t h_zune = 0;     // fused H items in zune decode semantics: k_resize_hbp's zune-class kernels
   bool stage_on = false;  // decode-once staging (option "entropy_once")
+  // the batch holds a four-component JPEG (option "jpeg_cmyk"): its entropy passes run their NC = 4
+  // instantiations (checkpoint records CkptN<4>), and sync2 / entropy_once / idct_fused stand down
+  bool nc4 = false;
   uint32_t max_slots = 1; // largest Huffman table count of an image (dynamic LDS of k_huff_sync/fix)
   uint32_t max_ac = 0;    // most distinct AC tables of a baseline JPEG (k_huff_sync multi-symbol lookups)
   size_t words_off = 0, words_bytes = 0;  // contiguous encoder bit buffers (zeroed per batch)
@@ -190,6 +193,7 @@ enum ListId {
   L_R16T, L_R16V, L_R16H,                                   // 16-bit resize: tap tables, V pass, H pass (dg_resize16.hip)
   L_PENC_ROW16,                                             // PNG re-encode of 16-bit samples: filter rows (k_penc_filter16)
   L_DESTUFF_WG,                                             // every kDsWgChunks-th destuff chunk (k_destuff_count / _write)
+  L_CMYK,                                                   // four planes -> RGB of a CMYK / YCCK JPEG (k_cmyk)
   L_COUNT
 };
 static_assert((int)L_COUNT <= 48, "Batch::lists");
@@ -527,6 +531,7 @@ class Context {
   bool progressive_ = true;             // option "progressive"
   bool png16_ = false;                  // option "png16": 16-bit PNGs decode on the GPU
   bool jpeg_h1v2_ = false;              // option "jpeg_h1v2": 4:4:0-style JPEGs decode on the GPU
+  bool jpeg_cmyk_ = false;              // option "jpeg_cmyk": Adobe CMYK / YCCK JPEGs decode on the GPU (to RGB)
   bool resize16_ = false;               // option "resize16": ... and resize to their bucket (dg_resize16.hip)
   bool penc16_ = false;                 // option "penc16": ... and go into the PNG re-encoder as 16-bit samples (dg_penc16.h)
   bool penc_dynamic_ = false;           // option "penc_dynamic": PNG re-encode with per-image Huffman codes where shorter

@@ -103,7 +103,7 @@ static uint32_t h_mfma_steps(const ResizePass &ps) {
 // Row stride of the decoded image a JPEG's or PNG's first pass (or k_copy) reads:
 // the RGB image or the PNG's pixels, or the luma plane of a gray JPEG.
 static uint32_t decoded_stride(const ImageDesc &d) {
-  return (d.fmt == kFmtPng || d.ncomp == 3) ? d.pix_stride : d.cbw[0] * 8;
+  return (d.fmt == kFmtPng || d.ncomp >= 3) ? d.pix_stride : d.cbw[0] * 8;
 }
 
 struct Layout {
@@ -130,7 +130,7 @@ struct SubmitArgs {
 
 // One image's buffer offsets: sizes first, pointers are patched after allocation.
 struct Offs {
-  size_t coef, ccnt, plane[3], pix, pass_dst[kStages], pass_coef[kStages], pass_bounds[kStages], pass_srcoff[kStages];
+  size_t coef, ccnt, plane[4], pix, pass_dst[kStages], pass_coef[kStages], pass_bounds[kStages], pass_srcoff[kStages];
   int pass_cache[kStages];    // Lanczos table cache entry of the pass (-1: tables in the scratch arena)
   bool pass_hit[kStages];     // ... already computed (no k_coeffs item)
   size_t final_off, tmp, out, ds, mk, chunk, stage;
@@ -415,6 +415,10 @@ void Context::layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl) {
   b.out_dev_off.assign(a.n, 0);
   b.out_direct.assign(a.n, 0);
   b.descs.reserve(a.n);
+  // a four-component JPEG (option "jpeg_cmyk") puts the whole batch on the entropy kernels' NC = 4
+  // instantiations; the paths that keep three DC sums (sync2, entropy_once, idct_fused) stand down for it
+  for (int i = 0; i < a.n; i++)
+    if (!b.plans[i].status && b.plans[i].fmt == kFmtJpeg && b.plans[i].hdr.ncomp == 4) b.nc4 = true;
   for (int i = 0; i < a.n; i++) {
     const ImagePlan &p = b.plans[i];
     if (p.status) continue;
@@ -587,18 +591,19 @@ void Context::layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl,
   // sparse blocks: k_huff_write's cooperative flush + k_idct_t only (not the
   // fused / decode-once writers, k_idct or k_band_dec; progressive scans
   // write whole blocks)
-  o.ccnt = (sparse_coef_ && idct_thread_ && !d.prog && !d.idct_fused && !entropy_once_)
+  o.ccnt = (sparse_coef_ && idct_thread_ && !d.prog && !d.idct_fused && !(entropy_once_ && !b.nc4))
                ? bl.CO.take((size_t)d.total_blocks, 64) + 1
                : 0;
-  for (int c = 0; c < 3; c++) o.plane[c] = (size_t)-1;  // allocated after the pass plan (not for k_band_dec)
+  for (int c = 0; c < 4; c++) o.plane[c] = (size_t)-1;  // allocated after the pass plan (not for k_band_dec)
   // (the RGB image of a colour JPEG is only materialised if no pass fuses it)
-  if (h.ncomp == 3) d.pix_stride = (uint32_t)align_up((size_t)W * 3, 16);
+  if (h.ncomp >= 3) d.pix_stride = (uint32_t)align_up((size_t)W * 3, 16);
 }
 
 // The entropy data of a baseline (sequential) JPEG: subsequences, checkpoints, destuff buffers.
 void Context::layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
   const JpegHeader &h = b.plans[i].hdr;
   const uint32_t sub_bits = bl.sub_bits;
+  const bool once = entropy_once_ && !b.nc4;  // (a batch with a four-component image: the default write pass)
   d.scan_len = (uint32_t)(h.scan_end - h.scan_off);
   // Per-image subsequence size (option "sub_density" T > 0): a lane's
   // decode time follows its symbols and blocks, not its bits, so images
@@ -616,11 +621,11 @@ void Context::layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &
   }
   // completed blocks go straight to plane pixels inside k_huff_write (not
   // with decode-once staging, whose k_huff_scatter writes coefficients)
-  d.idct_fused = (idct_fused_ && !entropy_once_) ? 1u : 0u;
+  d.idct_fused = (idct_fused_ && !once && !b.nc4) ? 1u : 0u;
   // k_huff_write splits each range at the sync pass's half-way checkpoint
   // (option "write_split"): needs that checkpoint, no restart markers and
   // the plain write path
-  if (write_split_ && d.ckpt && !d.idct_fused && !entropy_once_ && h.restart == 0 && d.sub_bits >= 1024 &&
+  if (write_split_ && d.ckpt && !d.idct_fused && !once && h.restart == 0 && d.sub_bits >= 1024 &&
       d.sub_bits / 2 / kCkptBits - 1 < num_ckpt(d.sub_bits))
     d.ckpt |= 2u;
   if (d.idct_fused) b.any_fused = true;
@@ -646,7 +651,7 @@ void Context::layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &
   d.ds_lsw = 0;
   while ((32u << d.ds_lsw) < d.sub_bits) d.ds_lsw++;
   o.ds = bl.L.take((size_t)ds_words_alloc(d.nsub, d.ds_lsw) * 4, 256);
-  if (entropy_once_ && d.sub_bits <= 8192) {  // decode-once staging (dg_entropy.h StageCtx)
+  if (once && d.sub_bits <= 8192) {  // decode-once staging (dg_entropy.h StageCtx)
     d.stage_cap = (d.sub_bits / 2 + d.sub_bits / 8 + 64 + 3) / 4;
     o.stage = bl.L.take((size_t)((d.nsub + 63) / 64) * d.stage_cap * 64 * 16, 256);
     b.stage_on = true;
@@ -798,7 +803,8 @@ int Context::plan_resize(const ImagePlan &p, Batch &b, BatchLayout &bl, ImageDes
         o.plane[c] = bl.L.take((size_t)d.cbw[c] * 8 * d.cbh[c] * 8 * (rec ? 2 : 1));
       }
   }
-  if (colour && !d.color_fused) o.pix = bl.L.take((size_t)d.pix_stride * H);
+  // (a CMYK / YCCK image is never fused: k_cmyk always writes its RGB image)
+  if ((colour && !d.color_fused) || (p.fmt == kFmtJpeg && d.ncomp == 4)) o.pix = bl.L.take((size_t)d.pix_stride * H);
   o.final_off = (size_t)yoff * cur_stride + (size_t)xoff * C;  // an uncomputed integral crop (k_copy's source)
   return last_stage;
 }
@@ -1019,7 +1025,7 @@ void Context::layout_batch_regions(Batch &b, BatchLayout &bl) {
     if (dd.fmt == kFmtJpeg && !dd.prog) b.ds_n += dd.nchunk;
   b.ds_state_off = (destuff_one_ && b.ds_n) ? L.take((size_t)(b.ds_n + 1) * 8) : 0;
   bl.subs_off = L.take(b.total_subs * sizeof(SubState));
-  bl.ckpt_off = L.take(std::max<uint64_t>(1, bl.ckpt_total) * sizeof(Ckpt));
+  bl.ckpt_off = L.take(std::max<uint64_t>(1, bl.ckpt_total) * (b.nc4 ? sizeof(CkptN<4>) : sizeof(Ckpt)));
   // fused IDCT leftovers: at most one carried-in block per subsequence, plus
   // the blocks of flushes with < 8 active lanes -- the tail of a wave, or
   // every block of an image with fewer subsequences than that.  Sized for
@@ -1141,7 +1147,7 @@ void Context::patch_jpeg(const JpegHeader &h, const uint8_t *src, const Slot &sl
     d.chunk = (uint64_t)(uintptr_t)(S + o.chunk);
   }
   for (int c = 0; c < h.ncomp; c++) d.plane[c] = o.plane[c] == (size_t)-1 ? 0 : (uint64_t)(uintptr_t)(S + o.plane[c]);
-  d.pix = h.ncomp == 3 && !d.color_fused ? (uint64_t)(uintptr_t)(S + o.pix) : 0;
+  d.pix = h.ncomp >= 3 && !d.color_fused ? (uint64_t)(uintptr_t)(S + o.pix) : 0;
 }
 
 // One record per scan of a progressive JPEG (descriptor di); level = 1 + the
@@ -1191,7 +1197,7 @@ void Context::prog_scan_records(const JpegHeader &h, const uint8_t *src, int di,
 // pix / plane and out are set).
 void Context::patch_passes(char *S, const Offs &o, int di, Batch &b) {
   ImageDesc &d = b.descs[di];
-  uint64_t cur = (d.fmt == kFmtPng || d.ncomp == 3) ? d.pix : d.plane[0];
+  uint64_t cur = (d.fmt == kFmtPng || d.ncomp >= 3) ? d.pix : d.plane[0];
   const uint64_t decoded = cur;
   for (int s = 0; s < kStages; s++) {
     ResizePass &ps = d.pass[s];
@@ -1356,9 +1362,9 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
     for (uint32_t c = 0; c < d.ncomp; c++) items += d.cbh[c] * ((d.cbw[c] + 63) / 64);  // kIdctBlocks
     if (!d.idct_fused && !(d.pass[0].mode & kHDecode))  // fused: k_huff_write (+ k_idct_list) / k_band_dec
       for (uint32_t it = 0; it < items; it += idct_thread_ ? kIdctItemStride : 1u) b.lists[L_IDCT].push_back({I, it});
-    if (d.ncomp == 3 && !d.color_fused) {
+    if (d.ncomp >= 3 && !d.color_fused) {  // the RGB image: k_color, or k_cmyk for four components
       uint32_t q = (d.width + 7) / 8 * d.height;
-      for (uint32_t it = 0; it < q; it += 256) b.lists[L_COLOR].push_back({I, it});
+      for (uint32_t it = 0; it < q; it += 256) b.lists[d.ncomp == 4 ? L_CMYK : L_COLOR].push_back({I, it});
     }
   }
   const bool hv = (d.pass[0].mode & kHVFused) != 0;

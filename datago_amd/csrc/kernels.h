@@ -13,22 +13,28 @@ void launch_destuff_write(hipStream_t st, const ImageDesc *imgs, const WgItem *l
 void launch_destuff_one(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg, uint64_t *state);
 // Entropy decode (one 256-thread workgroup per 256 subsequences of one image)
 // (sync/fix: 255 useful subsequences per workgroup, see kernels.hip)
-struct Ckpt;
+template <int NC>
+struct CkptN;
+using Ckpt = CkptN<3>;  // (dg_entropy.h)
+// nc4: the batch holds a four-component image (option "jpeg_cmyk"); the entropy kernels then run their
+// four-component instantiations, whose checkpoint records are CkptN<4>
 // stage: decode-once staging (ImageDesc::stage), see k_huff_scatter
 // max_slots: the largest ImageDesc::nslots in the batch (dynamic LDS for the tables);
 // max_ac: the most distinct AC tables of an image (multi-symbol lead-in lookups, 0 = off);
 // chain: further multi entries per state-only step of k_huff_sync (0..3, option "sync_chain")
 void launch_huff_sync(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                       const HuffTable *pool, SubState *subs, Ckpt *ck, BatchFlags *flags, bool stage,
-                      uint32_t max_slots, uint32_t max_ac, bool pair, bool two = false, uint32_t chain = 0);
+                      uint32_t max_slots, uint32_t max_ac, bool pair, bool two = false, uint32_t chain = 0,
+                      bool nc4 = false);
 void launch_huff_fix(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                      const HuffTable *pool, SubState *subs, Ckpt *ck, BatchFlags *flags, bool stage,
-                     uint32_t max_slots);
+                     uint32_t max_slots, bool nc4 = false);
 // one workgroup per image
-void launch_huff_scan(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg, SubState *subs);
+void launch_huff_scan(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg, SubState *subs,
+                      bool nc4 = false);
 void launch_huff_write(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                        const HuffTable *pool, const SubState *subs, BatchFlags *flags, uint32_t max_slots,
-                       const QuantTable *qpool, uint32_t pair, const Ckpt *ckpt);
+                       const QuantTable *qpool, uint32_t pair, const Ckpt *ckpt, bool nc4 = false);
 // fused IDCT leftovers (BatchFlags::idct_list), grid-strided over the device-side count
 void launch_idct_list(hipStream_t st, const ImageDesc *imgs, const QuantTable *qpool, const BatchFlags *flags,
                       uint32_t nwg);
@@ -41,6 +47,8 @@ void launch_idct(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint
                  const QuantTable *qpool);
 // upsample + colour convert: 256 x 4-pixel quads per workgroup
 void launch_color(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// four planes of a CMYK / YCCK image -> RGB (k_cmyk), same items as k_color
+void launch_cmyk(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // Lanczos coefficient tables: one workgroup per (image, stage)
 void launch_coeffs(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // resize passes of one stage: 256 output pixels (H) / 4-byte units (V) per workgroup

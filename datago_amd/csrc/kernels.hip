@@ -528,15 +528,14 @@ __device__ __forceinline__ void wg_time_store(const BatchFlags *flags, uint32_t 
 // step with the true decode and k_huff_fix finds nothing to repair.
 constexpr uint32_t kUseful = kSubPerWg - 1;
 
-__device__ __forceinline__ void store_sub(SubState &o, uint32_t in, uint32_t out, const RangeAcc &a,
+template <int NC>
+__device__ __forceinline__ void store_sub(SubState &o, uint32_t in, uint32_t out, const RangeAccN<NC> &a,
                                           const StageCtx *stg = nullptr) {
   o.in = in;
   o.out = out;
   o.m = a.m;
   o.n = a.n;
-  o.dc[0] = a.dc[0];
-  o.dc[1] = a.dc[1];
-  o.dc[2] = a.dc[2];
+  cpyn<NC>(o.dc, a.dc);
   if (stg && stg->on) {
     o.nstart = stg->started;
     o.nent = stg->n;
@@ -551,7 +550,10 @@ __device__ __forceinline__ void entropy_setprio(const BatchFlags *flags) {
   else if (p == 3) __builtin_amdgcn_s_setprio(3);
 }
 
-template <bool STAGE>
+// NC: 3, or 4 for a batch that holds a four-component image (option "jpeg_cmyk"): the DC sums, the
+// checkpoint records (CkptN<NC>) and SubState::dc carry the fourth component.  A three-component image of
+// such a batch decodes the same in either; its fourth sums stay 0.
+template <bool STAGE, int NC = 3>
 __global__ __launch_bounds__(256) void k_huff_sync(const ImageDesc *__restrict__ imgs,
                                                    const WgItem *__restrict__ list,
                                                    const HuffTable *__restrict__ pool,
@@ -600,8 +602,8 @@ __global__ __launch_bounds__(256) void k_huff_sync(const ImageDesc *__restrict__
   // must stage its whole range); thread 0's lead-in range belongs to the
   // previous workgroup and is not staged
   const bool stage = STAGE && im.stage != 0;
-  DG_GLOBAL Ckpt *ck =
-      (!stage && t > 0 && active && nck && im.ckpt) ? (DG_GLOBAL Ckpt *)ckpt + im.ckpt_base + (size_t)s * nck
+  DG_GLOBAL CkptN<NC> *ck =
+      (!stage && t > 0 && active && nck && im.ckpt) ? (DG_GLOBAL CkptN<NC> *)ckpt + im.ckpt_base + (size_t)s * nck
                                                      : nullptr;
   StageCtx sc;
   sc.on = stage && t > 0 && active;
@@ -609,7 +611,7 @@ __global__ __launch_bounds__(256) void k_huff_sync(const ImageDesc *__restrict__
   StageCtx *stg = STAGE ? &sc : nullptr;
   const DG_GLOBAL uint8_t *scan = gp<const uint8_t>(im.ds);
   const DG_GLOBAL uint32_t *mkp = gp<const uint32_t>(im.mk);
-  RangeAcc acc = {0, 0, 0, {0, 0, 0}};
+  RangeAccN<NC> acc = {0, 0, 0, {}};
   // entry state: exact for s == 0, otherwise the lead-in decode's guess
   const bool pair = (multi & 2u) != 0;
   const uint32_t chain = (multi & 1u) ? (multi >> 2) & 3u : 0u;  // chained multi entries per step (multi_chain)
@@ -744,7 +746,7 @@ __global__ __launch_bounds__(128) void k_huff_sync2(const ImageDesc *__restrict_
   wg_time_store(flags, blockIdx.x, t_start);
 }
 
-template <bool STAGE>
+template <bool STAGE, int NC = 3>
 __global__ __launch_bounds__(256) void k_huff_fix(const ImageDesc *__restrict__ imgs,
                                                   const WgItem *__restrict__ list,
                                                   const HuffTable *__restrict__ pool,
@@ -768,24 +770,22 @@ __global__ __launch_bounds__(256) void k_huff_fix(const ImageDesc *__restrict__ 
   const bool active = t < (int)kUseful && s < im.nsub;
   const uint32_t nck = num_ckpt(im.sub_bits);
   const bool stage = STAGE && im.stage != 0;
-  DG_GLOBAL Ckpt *ck =
-      (!stage && active && nck && im.ckpt) ? (DG_GLOBAL Ckpt *)ckpt + im.ckpt_base + (size_t)s * nck : nullptr;
+  DG_GLOBAL CkptN<NC> *ck =
+      (!stage && active && nck && im.ckpt) ? (DG_GLOBAL CkptN<NC> *)ckpt + im.ckpt_base + (size_t)s * nck : nullptr;
   StageCtx sc;
   sc.on = stage && active;
   sc.base = sc.on ? stage_range(im.stage, im.stage_cap, s) : nullptr;
   StageCtx *stg = STAGE ? &sc : nullptr;
   const DG_GLOBAL uint8_t *scan = gp<const uint8_t>(im.ds);
   const DG_GLOBAL uint32_t *mkp = gp<const uint32_t>(im.mk);
-  RangeAcc acc = {0, 0, 0, {0, 0, 0}};
+  RangeAccN<NC> acc = {0, 0, 0, {}};
   uint32_t orig_out = 0;
   if (active) {
     const SubState &o = base[s];
     orig_out = o.out;
     acc.m = o.m;
     acc.n = o.n;
-    acc.dc[0] = o.dc[0];
-    acc.dc[1] = o.dc[1];
-    acc.dc[2] = o.dc[2];
+    cpyn<NC>(acc.dc, o.dc);
     ex[t] = o.out;
     ins[t] = o.in;
   } else {
@@ -823,7 +823,6 @@ __device__ __forceinline__ SegAcc seg_combine(const SegAcc &a, const SegAcc &b) 
   if (b.m) return SegAcc{a.m + b.m, b.n, b.d0, b.d1, b.d2};
   return SegAcc{a.m, a.n + b.n, a.d0 + b.d0, a.d1 + b.d1, a.d2 + b.d2};
 }
-
 __global__ __launch_bounds__(256) void k_huff_scan(ImageDesc *__restrict__ imgs,
                                                    const WgItem *__restrict__ list,
                                                    SubState *__restrict__ subs) {
@@ -863,12 +862,63 @@ __global__ __launch_bounds__(256) void k_huff_scan(ImageDesc *__restrict__ imgs,
   }
 }
 
+// ... and with a fourth component's DC sum: the scan of a batch that holds a four-component image (option
+// "jpeg_cmyk").  A kernel of its own, so that k_huff_scan stays as it is.
+struct SegAcc4 {
+  uint32_t m, n;
+  int32_t d0, d1, d2, d3;
+};
+__device__ __forceinline__ SegAcc4 seg_combine(const SegAcc4 &a, const SegAcc4 &b) {
+  if (b.m) return SegAcc4{a.m + b.m, b.n, b.d0, b.d1, b.d2, b.d3};
+  return SegAcc4{a.m, a.n + b.n, a.d0 + b.d0, a.d1 + b.d1, a.d2 + b.d2, a.d3 + b.d3};
+}
+__global__ __launch_bounds__(256) void k_huff_scan4(ImageDesc *__restrict__ imgs,
+                                                    const WgItem *__restrict__ list,
+                                                    SubState *__restrict__ subs) {
+  __shared__ SegAcc4 sh[kSubPerWg];
+  const WgItem it = list[blockIdx.x];
+  ImageDesc &im = imgs[it.image];
+  SubState *base = subs + im.sub_base;
+  const int t = threadIdx.x;
+  SegAcc4 carry = {0, 0, 0, 0, 0, 0};
+  for (uint32_t c0 = 0; c0 < im.nsub; c0 += kSubPerWg) {
+    uint32_t i = c0 + t;
+    SegAcc4 v = {0, 0, 0, 0, 0, 0};
+    if (i < im.nsub) v = SegAcc4{base[i].m, base[i].n, base[i].dc[0], base[i].dc[1], base[i].dc[2], base[i].dc[3]};
+    sh[t] = v;
+    __syncthreads();
+    for (int off = 1; off < kSubPerWg; off <<= 1) {
+      SegAcc4 prev = (t >= off) ? sh[t - off] : SegAcc4{0, 0, 0, 0, 0, 0};
+      __syncthreads();
+      if (t >= off) sh[t] = seg_combine(prev, sh[t]);
+      __syncthreads();
+    }
+    SegAcc4 ex = (t == 0) ? SegAcc4{0, 0, 0, 0, 0, 0} : sh[t - 1];
+    SegAcc4 r = seg_combine(carry, ex);
+    if (i < im.nsub) {
+      base[i].seg = r.m;
+      base[i].nin = r.n;
+      base[i].dcin[0] = r.d0;
+      base[i].dcin[1] = r.d1;
+      base[i].dcin[2] = r.d2;
+      base[i].dcin[3] = r.d3;
+    }
+    carry = seg_combine(carry, sh[kSubPerWg - 1]);
+    __syncthreads();
+  }
+  if (t == 0) {
+    uint64_t decoded = im.blocks_per_seg ? (uint64_t)carry.m * im.blocks_per_seg + carry.n : carry.n;
+    if (decoded < im.total_blocks) im.status = 2;  // DG_ERR_CORRUPT: truncated entropy data
+  }
+}
+
 // Per-thread coefficient blocks in LDS, 64 int16 apart with their parts
 // swizzled by lane (WriteCtx::sw): the 16-byte zeroing stores and flush loads
 // of consecutive lanes cover distinct banks, as the 72-int16 stride of rounds
 // 1-4 did, in 32 instead of 36 KiB per workgroup (three workgroups per CU).
 constexpr int kBlkStride = 64;
 
+template <int NC>
 __global__ __launch_bounds__(256) void k_huff_write(ImageDesc *__restrict__ imgs,
                                                     const WgItem *__restrict__ list,
                                                     const HuffTable *__restrict__ pool,
@@ -916,7 +966,7 @@ __global__ __launch_bounds__(256) void k_huff_write(ImageDesc *__restrict__ imgs
     want = ss.out;
     if (split) {
       const uint32_t S = im.sub_bits, mid = s * S + S / 2, kmid = S / 2 / kCkptBits - 1;
-      const Ckpt c = ckpt[im.ckpt_base + (size_t)s * num_ckpt(S) + kmid];
+      const CkptN<NC> c = ((const CkptN<NC> *)ckpt)[im.ckpt_base + (size_t)s * num_ckpt(S) + kmid];
       const bool ok = mid < im.ds_bits && im.nmk == 0 && ss.m == 0 && c.m == 0 && st_rel(c.st) < 255u;
       if (!ok) {
         run = half == 0;  // the first lane takes the whole range
@@ -930,19 +980,18 @@ __global__ __launch_bounds__(256) void k_huff_write(ImageDesc *__restrict__ imgs
         ss.dcin[0] += ss.dc[0] - c.dc[0];
         ss.dcin[1] += ss.dc[1] - c.dc[1];
         ss.dcin[2] += ss.dc[2] - c.dc[2];
+        if (NC == 4) ss.dcin[NC - 1] += ss.dc[NC - 1] - c.dc[NC - 1];
       }
     }
   }
   if (run) {
-    WriteCtx w;
+    WriteCtxN<NC> w;
     w.blk = blk[t];
     w.sw = (((uint32_t)t >> 1) & 7u) << 3;
     w.coef = gp<int16_t>(im.coef);
     w.seg = ss.seg;
     w.nin = ss.nin;
-    w.pred[0] = ss.dcin[0];
-    w.pred[1] = ss.dcin[1];
-    w.pred[2] = ss.dcin[2];
+    cpyn<NC>(w.pred, ss.dcin);
     w.blocks_per_seg = im.blocks_per_seg;
     w.total_blocks = im.total_blocks;
     w.cur = -1;
@@ -962,7 +1011,7 @@ __global__ __launch_bounds__(256) void k_huff_write(ImageDesc *__restrict__ imgs
 #pragma unroll
       for (int i = 0; i < 8; i++) p[i] = zero;
     }
-    RangeAcc acc;
+    RangeAccN<NC> acc;
     decode_range<true, HuffTable, true>(im, tabs, gp<const uint8_t>(im.ds), gp<const uint32_t>(im.mk), s, in,
                                         acc, &w, nullptr, false, 0, nullptr, nullptr, 0xFFu, pair, a0o, a1o);
     if (acc.out != want || (s == 0 && (flags->debug & kDbgForceWriteMismatch))) {
@@ -1723,6 +1772,94 @@ __global__ __launch_bounds__(256) void k_color(const ImageDesc *__restrict__ img
   } else {
     const uint32_t n = (im.width - x0) * 3;
     for (uint32_t i = 0; i < n; i++) dst[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+  }
+}
+
+// Four-component Adobe JPEGs (option "jpeg_cmyk": CS_CMYK = APP14 transform 0, CS_YCCK = transform 2) to
+// the RGB image, where k_color runs for a three-component one: 8 pixels per lane.  Every component is
+// upsampled by its own ratio with the image's decode semantics; YCCK turns components 0..2 into RGB with
+// the semantics' own conversion and takes c, m, y = 255 - r, g, b; then R, G, B = blinn(c, k), blinn(m, k),
+// blinn(y, k), blinn(a, b) = (t + (t >> 8)) >> 8 with t = a b + 128 (zune-jpeg's color_convert_cymk_to_rgb /
+// _ycck_to_rgb = stb_image's blinn_8x8, recalled and parity-unpinned; libjpeg-turbo hands CMYK back
+// unconverted, so semantics 0 takes the same last step on its own planes).  t + (t >> 8) <= 65,407: the
+// step runs on pixel pairs in packed 16-bit lanes (v_pk_mad_u16, v_pk_lshrrev_b16, v_pk_add_u16).
+typedef unsigned short u16x2c __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void cmyk_up8(const ImageDesc &im, uint32_t c, uint32_t x0, uint32_t y, int32_t o[8]) {
+  if (im.sem)
+    upsample8_zune(gp<const uint8_t>(im.plane[c]), im.cbw[c] * 8, im.hmax / im.ch[c], im.vmax / im.cv[c],
+                   im.cbh[c] * 8, x0, y, o, false);
+  else
+    upsample8(gp<const uint8_t>(im.plane[c]), im.cbw[c] * 8, im.hmax / im.ch[c], im.vmax / im.cv[c], im.cdsw[c],
+              im.cdsh[c], x0, y, o, false);
+}
+__global__ __launch_bounds__(256) void k_cmyk(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  const WgItem it = list[blockIdx.x];
+  const ImageDesc &im = imgs[it.image];
+  const uint32_t ow = (im.width + 7) / 8;  // octets per row
+  const uint32_t q = it.item0 + threadIdx.x;
+  if (q >= ow * im.height) return;
+  const uint32_t y = q / ow, x0 = (q - y * ow) * 8;
+  int32_t C0[8], C1[8], C2[8], K[8];
+  cmyk_up8(im, 0, x0, y, C0);
+  cmyk_up8(im, 1, x0, y, C1);
+  cmyk_up8(im, 2, x0, y, C2);
+  cmyk_up8(im, 3, x0, y, K);
+  if (im.colorspace == CS_YCCK) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      uint8_t r, g, b;
+      if (im.sem)
+        ycc_to_rgb_zune(C0[k], C1[k], C2[k], r, g, b);
+      else
+        ycc_to_rgb(C0[k], C1[k], C2[k], r, g, b);
+      C0[k] = 255 - (int32_t)r;
+      C1[k] = 255 - (int32_t)g;
+      C2[k] = 255 - (int32_t)b;
+    }
+  }
+  // blinn on pixel pairs (2i, 2i + 1); the results are bytes in the low half of each 16-bit lane
+  const u16x2c c128 = {128, 128};
+  uint32_t R[4], G[4], B[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const u16x2c kk = {(unsigned short)K[2 * i], (unsigned short)K[2 * i + 1]};
+    const u16x2c c = {(unsigned short)C0[2 * i], (unsigned short)C0[2 * i + 1]};
+    const u16x2c m = {(unsigned short)C1[2 * i], (unsigned short)C1[2 * i + 1]};
+    const u16x2c yy = {(unsigned short)C2[2 * i], (unsigned short)C2[2 * i + 1]};
+    const u16x2c tr = c * kk + c128, tg = m * kk + c128, tb = yy * kk + c128;
+    R[i] = __builtin_bit_cast(uint32_t, (u16x2c)((tr + (tr >> 8)) >> 8));
+    G[i] = __builtin_bit_cast(uint32_t, (u16x2c)((tg + (tg >> 8)) >> 8));
+    B[i] = __builtin_bit_cast(uint32_t, (u16x2c)((tb + (tb >> 8)) >> 8));
+  }
+  // pair i holds pixels 2i (bytes 0) and 2i + 1 (byte 2) of a channel -> R G B R | G B R G | B R G B per 4 pixels
+  uint32_t w[6];
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const uint32_t r0 = R[2 * h], g0 = G[2 * h], b0 = B[2 * h], r1 = R[2 * h + 1], g1 = G[2 * h + 1], b1 = B[2 * h + 1];
+    const uint32_t rg = __builtin_amdgcn_perm(g0, r0, 0x06020400u);  // R0 G0 R1 G1 (pixels 0, 1 of the half)
+    const uint32_t rg2 = __builtin_amdgcn_perm(g1, r1, 0x06020400u);  // R2 G2 R3 G3
+    const uint32_t bb = __builtin_amdgcn_perm(b1, b0, 0x06040200u);   // B0 B1 B2 B3
+    w[3 * h] = __builtin_amdgcn_perm(bb, rg, 0x02040100u);            // R0 G0 B0 R1
+    w[3 * h + 1] = __builtin_amdgcn_perm(__builtin_amdgcn_perm(bb, rg, 0x0C0C0503u), rg2, 0x01000504u);  // G1 B1 R2 G2
+    w[3 * h + 2] = __builtin_amdgcn_perm(bb, rg2, 0x07030206u);       // B2 R3 G3 B3
+  }
+  DG_GLOBAL uint8_t *dst = gp<uint8_t>(im.pix) + (size_t)y * im.pix_stride + x0 * 3;
+  if (x0 + 8 <= im.width) {
+    // x0 * 3 is a multiple of 24 and pix_stride of 16: the 24 bytes are 16 + 8 or 8 + 16 aligned
+    if ((x0 & 8u) == 0) {
+      *(DG_GLOBAL u32x4 *)dst = u32x4{w[0], w[1], w[2], w[3]};
+      *(DG_GLOBAL u32x2 *)(dst + 16) = u32x2{w[4], w[5]};
+    } else {
+      *(DG_GLOBAL u32x2 *)dst = u32x2{w[0], w[1]};
+      *(DG_GLOBAL u32x4 *)(dst + 8) = u32x4{w[2], w[3], w[4], w[5]};
+    }
+  } else {
+    const uint32_t n = (im.width - x0) * 3;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t j = i >> 2;
+      const uint32_t wj = j == 0 ? w[0] : j == 1 ? w[1] : j == 2 ? w[2] : j == 3 ? w[3] : j == 4 ? w[4] : w[5];
+      dst[i] = (uint8_t)(wj >> (8 * (i & 3)));
+    }
   }
 }
 
@@ -3438,12 +3575,15 @@ void launch_destuff_one(hipStream_t st, ImageDesc *imgs, const WgItem *list, uin
 // per workgroup, 8 resident workgroups per CU instead of 6
 void launch_huff_sync(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                       const HuffTable *pool, SubState *subs, Ckpt *ck, BatchFlags *flags, bool stage,
-                      uint32_t max_slots, uint32_t max_ac, bool pair, bool two, uint32_t chain) {
+                      uint32_t max_slots, uint32_t max_ac, bool pair, bool two, uint32_t chain, bool nc4) {
   if (!nwg) return;
   const size_t lds = (size_t)max_slots * sizeof(HuffTable) + ((size_t)max_ac << kMultiBits) * 2;
   // bit 0: multi-symbol lookups, bit 1: pair steps, bits 2-3: chained multi entries per step (k_huff_sync)
   const uint32_t multi = (max_ac ? 1u : 0u) | (pair ? 2u : 0u) | ((chain & 3u) << 2);
-  if (two && !stage && !pair)  // two chains per lane (k_huff_sync2: no staging, no pair steps)
+  if (nc4)  // a batch with a four-component image: the NC = 4 instantiation (such a batch never stages, and
+            // never takes k_huff_sync2)
+    hipLaunchKernelGGL((k_huff_sync<false, 4>), dim3(nwg), dim3(256), lds, st, imgs, list, pool, subs, ck, flags, multi);
+  else if (two && !stage && !pair)  // two chains per lane (k_huff_sync2: no staging, no pair steps)
     hipLaunchKernelGGL(k_huff_sync2, dim3(nwg), dim3(128), lds, st, imgs, list, pool, subs, ck, flags, multi);
   else if (stage)
     hipLaunchKernelGGL(k_huff_sync<true>, dim3(nwg), dim3(256), lds, st, imgs, list, pool, subs, ck, flags, multi);
@@ -3452,23 +3592,32 @@ void launch_huff_sync(hipStream_t st, const ImageDesc *imgs, const WgItem *list,
 }
 void launch_huff_fix(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                      const HuffTable *pool, SubState *subs, Ckpt *ck, BatchFlags *flags, bool stage,
-                     uint32_t max_slots) {
+                     uint32_t max_slots, bool nc4) {
   if (!nwg) return;
   const size_t lds = (size_t)max_slots * sizeof(HuffTable);
-  if (stage)
+  if (nc4)
+    hipLaunchKernelGGL((k_huff_fix<false, 4>), dim3(nwg), dim3(256), lds, st, imgs, list, pool, subs, ck, flags);
+  else if (stage)
     hipLaunchKernelGGL(k_huff_fix<true>, dim3(nwg), dim3(256), lds, st, imgs, list, pool, subs, ck, flags);
   else
     hipLaunchKernelGGL(k_huff_fix<false>, dim3(nwg), dim3(256), lds, st, imgs, list, pool, subs, ck, flags);
 }
-void launch_huff_scan(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg, SubState *subs) {
-  DG_LAUNCH(k_huff_scan, nwg, st, imgs, list, subs);
+void launch_huff_scan(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg, SubState *subs, bool nc4) {
+  if (nc4)
+    DG_LAUNCH(k_huff_scan4, nwg, st, imgs, list, subs);
+  else
+    DG_LAUNCH(k_huff_scan, nwg, st, imgs, list, subs);
 }
 void launch_huff_write(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                        const HuffTable *pool, const SubState *subs, BatchFlags *flags, uint32_t max_slots,
-                       const QuantTable *qpool, uint32_t pair, const Ckpt *ckpt) {
+                       const QuantTable *qpool, uint32_t pair, const Ckpt *ckpt, bool nc4) {
   if (!nwg) return;
-  hipLaunchKernelGGL(k_huff_write, dim3(nwg), dim3(256), (size_t)max_slots * sizeof(HuffTable), st, imgs, list,
-                     pool, subs, flags, qpool, pair, ckpt);
+  if (nc4)
+    hipLaunchKernelGGL(k_huff_write<4>, dim3(nwg), dim3(256), (size_t)max_slots * sizeof(HuffTable), st, imgs, list,
+                       pool, subs, flags, qpool, pair, ckpt);
+  else
+    hipLaunchKernelGGL(k_huff_write<3>, dim3(nwg), dim3(256), (size_t)max_slots * sizeof(HuffTable), st, imgs, list,
+                       pool, subs, flags, qpool, pair, ckpt);
 }
 void launch_idct_list(hipStream_t st, const ImageDesc *imgs, const QuantTable *qpool, const BatchFlags *flags,
                       uint32_t nwg) {
@@ -3487,6 +3636,9 @@ void launch_idct(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint
 }
 void launch_color(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   DG_LAUNCH(k_color, nwg, st, imgs, list);
+}
+void launch_cmyk(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  DG_LAUNCH(k_cmyk, nwg, st, imgs, list);
 }
 void launch_coeffs(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   DG_LAUNCH(k_coeffs, nwg, st, imgs, list);

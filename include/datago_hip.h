@@ -46,7 +46,8 @@ extern "C" {
 typedef enum dg_status {
   DG_OK = 0,
   DG_ERR_UNSUPPORTED = 1, /* valid image the GPU path does not decode (arithmetic, 12-bit,
-                             CMYK, non-JPEG/PNG...; 16-bit PNG unless option "png16" is set,
+                             CMYK / YCCK unless option "jpeg_cmyk" is set, non-JPEG/PNG...;
+                             16-bit PNG unless option "png16" is set,
                              and then still one that needs the resize or an encoder unless
                              "resize16" / "penc16" are set too):
                              caller keeps its CPU path */
@@ -270,6 +271,26 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 decode_semantics 1, zune-jpeg's upsample_vertical: (3 * near + far + 2) >> 2 on both
  *                 phases, the far row clamped to the MCU-padded rows (recalled from the crate's source
  *                 and parity-unpinned, like the rest of that mode).  Any other value: DG_ERR_INVALID
+ *   "jpeg_cmyk"   1 = decode four-component JPEGs with an Adobe APP14 segment of transform 0 (CMYK) or 2
+ *                 (YCCK) -- what Photoshop and print workflows export -- to RGB8 (meta channels 3, bit depth
+ *                 8, image 0.25's mapping for them), baseline and progressive.  Default 0:
+ *                 DG_ERR_UNSUPPORTED ("CMYK/2-component JPEG"), as dg_probe's gpu_supported reports, which
+ *                 describes the default options.  With 1 a 4-component 8-bit Huffman frame is accepted
+ *                 when every component's ratio to the largest factors is 1x1, 2x1 or 2x2 (1x2 too when
+ *                 "jpeg_h1v2" is set), the MCU has at most 10 blocks and a sequential scan names all four
+ *                 components.  Still DG_ERR_UNSUPPORTED, each with a dg_last_error text of its own: no
+ *                 Adobe segment (inverted or not is then ambiguous), transform 1, two-component frames,
+ *                 and a sequential file that names more than six distinct Huffman tables (what a
+ *                 workgroup of the entropy kernels holds; real files name four).  Every component is
+ *                 upsampled by its own ratio in the context's decode semantics.  Transform 2 converts
+ *                 components 0..2 with the semantics' YCbCr -> RGB and takes c, m, y = 255 - r, g, b;
+ *                 transform 0 takes the samples.  Then, in both semantics, R, G, B = blinn(c, k),
+ *                 blinn(m, k), blinn(y, k) with blinn(a, b) = (t + (t >> 8)) >> 8, t = a * b + 128
+ *                 (= (a * b + 127) / 255): zune-jpeg's color_convert_cymk_to_rgb / _ycck_to_rgb, recalled
+ *                 from the crate's source and parity-unpinned like the rest of that mode; libjpeg-turbo
+ *                 hands CMYK back unconverted, so decode_semantics 0 takes the same last step on its own
+ *                 planes (which equal 255 - Pillow's CMYK image).  ICC profiles are ignored, as the
+ *                 reference ignores them.  Any other value: DG_ERR_INVALID
  *   "png16"       1 = decode 16-bit PNGs on the GPU (default 0: DG_ERR_UNSUPPORTED, as dg_probe's
  *                 gpu_supported reports, which describes the default options).  Colour types 0/2/4/6
  *                 become Luma16 / Rgb16 / LumaA16 / Rgba16 (a tRNS key adds a 16-bit alpha, 0 or
