@@ -321,6 +321,16 @@ DG_HD int32_t wc_index(const WriteCtxBase &w, uint32_t in_seg) {
   return g < w.total_blocks ? (int32_t)g : -1;
 }
 
+// The same for the write pass's multiscan instantiation (option "jpeg_multiscan"): block g of a scan
+// descriptor lands at the index the parent's MCU-interleaved order gives it (ms_index, dg_types.h); flushes,
+// sparse masks and partial-block writes then follow the mapped index unchanged.
+template <bool MS>
+DG_HD int32_t wc_index_ms(const ImageDesc &im, const WriteCtxBase &w, uint32_t in_seg) {
+  const int32_t g = wc_index(w, in_seg);
+  if (MS && g >= 0 && im.ms.role == kMsScan) return (int32_t)ms_index(im.ms, (uint32_t)g);
+  return g;
+}
+
 DG_HD void wc_begin(WriteCtxBase &w, int32_t idx, uint32_t zs) {
   w.cur = idx;
   w.zs = zs;
@@ -689,7 +699,8 @@ DG_HD uint32_t lead_in(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL uin
 //   tabs: Huffman tables indexed by slot (im.dc_slot / im.ac_slot)
 //   ck: this subsequence's checkpoint records (nullptr: none); merge: the
 //   records hold a previous decode of this range whose exit state was old_out.
-template <bool WRITE, class TAB, bool COOP = false, int NC = 3>
+//   MS: blocks of a scan descriptor are stored through wc_index_ms (k_huff_write of a batch with a multiscan image)
+template <bool WRITE, class TAB, bool COOP = false, int NC = 3, bool MS = false>
 DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL uint8_t *stream,
                         const DG_GLOBAL uint32_t *mk,
                         uint32_t s, uint32_t in, RangeAccN<NC> &acc, typename NoDeduce<WriteCtxN<NC>>::type *w,
@@ -731,7 +742,7 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
   bool pending = false;  // COOP: a completed block awaits the wave's flush
   if (WRITE) {
     w->cur = -1;
-    if (z > 0) wc_begin(*w, w->nin > 0 ? wc_index(*w, w->nin - 1) : -1, z);
+    if (z > 0) wc_begin(*w, w->nin > 0 ? wc_index_ms<MS>(im, *w, w->nin - 1) : -1, z);
   }
   // Per symbol only one compare against the next "event" (restart marker,
   // checkpoint, end of range); the Huffman tables of the current block are
@@ -846,10 +857,10 @@ DG_HD void decode_range(const ImageDesc &im, const TAB *tabs, const DG_GLOBAL ui
       addn(w->pred, comp, vdc);
       if (isdc) {
         if (COOP) {
-          w->cur = wc_index(*w, w->nin);
+          w->cur = wc_index_ms<MS>(im, *w, w->nin);
           w->zs = 0;
         } else {
-          wc_begin(*w, wc_index(*w, w->nin), 0);
+          wc_begin(*w, wc_index_ms<MS>(im, *w, w->nin), 0);
         }
         w->nin++;
       }

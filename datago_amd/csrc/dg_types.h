@@ -325,6 +325,55 @@ struct EncDesc {
   uint8_t q[2][64];    // quantisation tables, natural order
 };
 
+// ---- non-interleaved baseline JPEG (option "jpeg_multiscan"): a sequential file whose scans each carry one or
+// two of the frame's three components.  The image keeps one descriptor, the parent (geometry, planes, resize
+// plan, output, one MCU-interleaved coef / ccnt buffer); each scan gets an entropy-only descriptor of its own
+// behind the batch's image descriptors (stream, subsequences, tables, restart interval; coef / ccnt are the
+// parent's).  A scan decodes its blocks in its own order -- a one-component scan the component's own grid
+// ceil(cdsw / 8) x ceil(cdsh / 8) row by row (T.81 A.2.2), an interleaved one the frame's MCU grid with the MCU
+// cut down to its components -- and k_huff_write's multiscan instantiation stores block g of the scan at
+// ms_index(map, g) of the parent.  The blocks between a component's own grid and the MCU-padded grid are coded
+// by no scan: k_ms_zero clears them before the write.
+constexpr uint32_t kMsParent = 1, kMsScan = 2;
+struct ScanMap {
+  uint32_t role;        // 0: an ordinary image, kMsParent, kMsScan
+  uint32_t div, recip;  // one component: its own grid width; interleaved: the scan's blocks per MCU.
+                        // recip = min(floor(2^32 / div), 2^32 - 1)
+  uint32_t mcux, bpm;   // the parent's MCUs per row and blocks per MCU
+  uint8_t inter;        // 1: two components, interleaved
+  uint8_t lh, lv;       // one component: log2 of its sampling factors (1, 2 or 4)
+  uint8_t na;           // interleaved: blocks of the scan's first component per MCU
+  uint8_t cf0, cf1;     // first block of the scan's first / second component within the parent's MCU
+  uint8_t pad[2];
+  uint32_t pad64[9];    // 64 bytes: ImageDesc stays a whole number of 64-byte lines (it was 21 of them), so
+                        // every descriptor of the array starts on one, as before
+};
+static_assert(sizeof(ScanMap) == 64, "ScanMap is one 64-byte line");
+DG_HD uint32_t ms_recip(uint32_t div) { return div <= 1u ? 0xFFFFFFFFu : (uint32_t)(0x100000000ull / div); }
+// g / div for any g: the multiply-high is the quotient or one below it
+DG_HD uint32_t ms_div(uint32_t g, uint32_t div, uint32_t recip, uint32_t &rem) {
+  uint32_t q = (uint32_t)(((uint64_t)g * recip) >> 32);
+  uint32_t r = g - q * div;
+  const bool up = r >= div;
+  q += up ? 1u : 0u;
+  r -= up ? div : 0u;
+  rem = r;
+  return q;
+}
+// Block (by, bx) of a component (first block cf of the MCU, sampling 1 << lh by 1 << lv) in MCU-interleaved order
+DG_HD uint32_t ms_block_index(uint32_t mcux, uint32_t bpm, uint32_t cf, uint32_t lh, uint32_t lv, uint32_t by,
+                              uint32_t bx) {
+  const uint32_t hm = (1u << lh) - 1u, vm = (1u << lv) - 1u;
+  return ((by >> lv) * mcux + (bx >> lh)) * bpm + cf + ((by & vm) << lh) + (bx & hm);
+}
+// Decode index g of a scan -> block index of the parent
+DG_HD uint32_t ms_index(const ScanMap &m, uint32_t g) {
+  uint32_t r;
+  const uint32_t q = ms_div(g, m.div, m.recip, r);
+  if (m.inter) return q * m.bpm + (r < m.na ? m.cf0 + r : m.cf1 + (r - m.na));
+  return ms_block_index(m.mcux, m.bpm, m.cf0, m.lh, m.lv, q, r);
+}
+
 struct ImageDesc {
   // ---- entropy stream
   uint64_t scan;            // device address of the first raw entropy-coded byte
@@ -397,7 +446,37 @@ struct ImageDesc {
   PngDesc png;
   AlphaOp aop[kAlphaPoints];
   EncDesc enc;
+  ScanMap ms;               // option "jpeg_multiscan": the parent of scan descriptors, or one of them
 };
+
+static_assert(sizeof(ImageDesc) % 64 == 0, "descriptors start on 64-byte lines");
+
+// The map of a scan of ns (1 or 2) components comp[] of parent `par` (its geometry set), and the blocks the
+// scan codes: a component's own grid, or the frame's MCU grid times the scan's blocks per MCU.
+DG_HD ScanMap ms_scan_map(const ImageDesc &par, uint32_t ns, const int *comp, uint32_t &total_blocks) {
+  ScanMap m = {};
+  m.role = kMsScan;
+  m.mcux = par.mcux;
+  m.bpm = par.bpm;
+  const uint32_t c0 = (uint32_t)comp[0];
+  m.cf0 = (uint8_t)par.cfirst[c0];
+  if (ns == 1) {  // the component's own grid, row by row (T.81 A.2.2)
+    const uint32_t gw = (par.cdsw[c0] + 7) / 8, gh = (par.cdsh[c0] + 7) / 8;
+    m.div = gw;
+    m.lh = (uint8_t)(par.ch[c0] >> 1);  // log2 of 1, 2, 4
+    m.lv = (uint8_t)(par.cv[c0] >> 1);
+    total_blocks = gw * gh;
+  } else {  // the frame's MCU grid, the MCU cut down to the scan's two components (A.2.3)
+    const uint32_t c1 = (uint32_t)comp[1];
+    m.inter = 1;
+    m.na = (uint8_t)(par.ch[c0] * par.cv[c0]);
+    m.div = m.na + par.ch[c1] * par.cv[c1];
+    m.cf1 = (uint8_t)par.cfirst[c1];
+    total_blocks = par.mcux * par.mcuy * m.div;
+  }
+  m.recip = ms_recip(m.div);
+  return m;
+}
 
 // ---- progressive JPEG (ImageDesc::prog > 0).  The coefficient blocks are
 // zeroed (k_prog_zero), then every scan is decoded by one wave of k_prog_scan

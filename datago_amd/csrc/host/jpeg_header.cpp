@@ -40,18 +40,29 @@ static void fail(JpegHeader &h, int st, const char *why) {
   h.why = why;
 }
 
-void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v2, bool allow_cmyk) {
+void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v2, bool allow_cmyk,
+                       bool allow_multiscan) {
   h = JpegHeader();
   if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(h, JH_CORRUPT, "not a JPEG (no SOI)");
-  bool saw_sof = false;
+  bool saw_sof = false, ms_eoi = false;
+  uint32_t ms_coded = 0;  // multiscan: components some scan has coded
   size_t p = 2;
   for (;;) {
     while (p < n && d[p] != 0xFF) p++;
     while (p < n && d[p] == 0xFF) p++;
-    if (p >= n) return fail(h, JH_CORRUPT, "truncated before SOS");
+    if (p >= n) {
+      if (h.multiscan) break;  // no EOI after the last scan read (whether every component was coded: below)
+      return fail(h, JH_CORRUPT, "truncated before SOS");
+    }
     int m = d[p++];
     if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
-    if (m == 0xD9) return fail(h, JH_CORRUPT, "EOI before SOS");
+    if (m == 0xD9) {
+      if (h.multiscan) {
+        ms_eoi = true;
+        break;
+      }
+      return fail(h, JH_CORRUPT, "EOI before SOS");
+    }
     if (p + 2 > n) return fail(h, JH_CORRUPT, "truncated marker");
     int L = rd16(d + p);
     if (L < 2 || p + (size_t)L > n) return fail(h, JH_CORRUPT, "bad marker length");
@@ -59,6 +70,9 @@ void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v
     int len = L - 2;
     if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
       // SOFn
+      // (the multiscan walk reads markers after a scan: a second frame header would swap the components under
+      // the scans already recorded)
+      if (h.multiscan) return fail(h, JH_CORRUPT, "frame header after a scan of a non-interleaved JPEG");
       if (len < 6) return fail(h, JH_CORRUPT, "short SOF");
       h.sof = m;
       h.progressive = (m == 0xC2 || m == 0xC6 || m == 0xCA || m == 0xCE);
@@ -104,6 +118,16 @@ void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v
       while (o < len) {
         int pq = s[o] >> 4, tq = s[o] & 15;
         if (tq > 3 || pq > 1 || o + 1 + 64 * (pq + 1) > len) return fail(h, JH_CORRUPT, "bad DQT");
+        if (h.multiscan && h.qpresent[tq]) {
+          // between the scans of a non-interleaved file: the IDCT takes one table per component, so a table
+          // some component uses must stay as it is
+          bool differs = false, used = false;
+          for (int k = 0; k < 64; k++)
+            differs |= h.q[tq][kNat[k]] != (pq ? (uint16_t)rd16(s + o + 1 + 2 * k) : (uint16_t)s[o + 1 + k]);
+          for (int c = 0; c < h.ncomp; c++) used |= h.comp[c].tq == tq;
+          if (differs && used)
+            return fail(h, JH_UNSUPPORTED, "quantisation table redefined between the scans of a non-interleaved JPEG");
+        }
         for (int k = 0; k < 64; k++)
           h.q[tq][kNat[k]] = pq ? (uint16_t)rd16(s + o + 1 + 2 * k) : (uint16_t)s[o + 1 + k];
         h.qpresent[tq] = true;
@@ -134,7 +158,58 @@ void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v
         h.comp[c].ta = s[2 + 2 * i] & 15;
         if (h.comp[c].td > 3 || h.comp[c].ta > 3) return fail(h, JH_CORRUPT, "bad table selector");
       }
+      if (h.multiscan && (int)h.scans.size() >= h.ncomp)
+        return fail(h, JH_UNSUPPORTED, "non-interleaved JPEG with more scans than components");
       h.scan_off = p + (size_t)L;
+      // context option jpeg_multiscan: a three-component sequential file whose first scan names fewer
+      // components than the frame.  Every scan is walked as a progressive file's are; a file whose first scan
+      // is fully interleaved never comes here.
+      if (allow_multiscan && !h.progressive && (h.sof == 0xC0 || h.sof == 0xC1) && h.precision == 8 && h.ncomp == 3 &&
+          (h.multiscan || ns < h.ncomp)) {
+        h.multiscan = true;
+        JpegScan sc;
+        sc.ns = ns;
+        sc.ss = s[1 + 2 * ns];
+        sc.se = s[2 + 2 * ns];
+        sc.ah = s[3 + 2 * ns] >> 4;
+        sc.al = s[3 + 2 * ns] & 15;
+        sc.restart = h.restart;  // DRI may change between scans
+        if (sc.ss != 0 || sc.se != 63 || sc.ah != 0 || sc.al != 0)
+          return fail(h, JH_CORRUPT, "spectral selection or successive approximation in a sequential scan");
+        for (int i = 0; i < ns; i++) {
+          const int c = h.scan_comp[i];
+          if (ms_coded & (1u << c)) return fail(h, JH_CORRUPT, "component coded twice in a non-interleaved JPEG");
+          ms_coded |= 1u << c;
+          const JpegComponent &k = h.comp[c];
+          if (!h.dc[k.td].present || !h.ac[k.ta].present) return fail(h, JH_CORRUPT, "missing Huffman table");
+          sc.comp[i] = c;
+          // the tables in force now: writers of such files re-send a DHT under one id before every scan
+          sc.dc_tab[i] = (int)h.tables.size();
+          h.tables.push_back(h.dc[k.td]);
+          sc.ac_tabs[i] = (int)h.tables.size();
+          h.tables.push_back(h.ac[k.ta]);
+        }
+        // the scan's data ends at the first marker that is not RSTn, or with the file
+        sc.off = p + (size_t)L;
+        size_t q = sc.off;
+        bool marker = false;
+        while (q < n) {
+          const uint8_t *f = (const uint8_t *)memchr(d + q, 0xFF, n - q);
+          if (!f || (size_t)(f - d) + 1 >= n) break;
+          q = (size_t)(f - d);
+          const uint8_t c = d[q + 1];
+          if (c != 0x00 && c != 0xFF && !(c >= 0xD0 && c <= 0xD7)) {
+            marker = true;
+            break;
+          }
+          q++;
+        }
+        sc.end = marker ? q : n;
+        h.scans.push_back(sc);
+        if (!marker) break;  // cut inside this scan: the entropy decode reports it
+        p = q;
+        continue;
+      }
       if (h.progressive) {
         // T.81 G.1.2 scan parameters (libjpeg jdphuff.c start_pass_phuff_decoder checks)
         JpegScan sc;
@@ -210,7 +285,21 @@ void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v
     if (h.adobe_transform != 0 && h.adobe_transform != 2)
       return fail(h, JH_UNSUPPORTED, "4-component JPEG with an unknown Adobe transform");
   }
-  if (!h.progressive && h.scan_ncomp != h.ncomp) return fail(h, JH_UNSUPPORTED, "non-interleaved multi-scan JPEG");
+  if (h.multiscan) {
+    // (what the walk was entered with still holds: no marker it reads changes the frame)
+    if (h.progressive || h.ncomp != 3) return fail(h, JH_CORRUPT, "frame header after a scan of a non-interleaved JPEG");
+    if (ms_coded != 7u)
+      return ms_eoi ? fail(h, JH_UNSUPPORTED, "non-interleaved JPEG with a component that no scan codes")
+                    : fail(h, JH_CORRUPT, "non-interleaved JPEG truncated before every component was coded");
+    for (int c = 0; c < h.ncomp; c++)
+      if (h.comp[c].h == 3 || h.comp[c].v == 3)
+        return fail(h, JH_UNSUPPORTED, "non-interleaved JPEG with a sampling factor of 3");
+    h.scan_off = h.scans.front().off;
+    h.scan_end = h.scans.back().end;
+  } else if (!h.progressive && h.scan_ncomp != h.ncomp) {
+    if (allow_multiscan && h.ncomp == 4) return fail(h, JH_UNSUPPORTED, "non-interleaved four-component JPEG");
+    return fail(h, JH_UNSUPPORTED, "non-interleaved multi-scan JPEG");
+  }
   if (h.progressive) {
     // coefficient precision after the last scan (libjpeg coef_bits): the DC and
     // AC 1..9 must end exact, or libjpeg would smooth blocks (jdcoefct.c smoothing_ok)
@@ -258,7 +347,7 @@ void parse_jpeg_header(const uint8_t *d, size_t n, JpegHeader &h, bool allow_h1v
   }
   for (int c = 0; c < h.ncomp; c++) {
     if (!h.qpresent[h.comp[c].tq]) return fail(h, JH_CORRUPT, "missing quantisation table");
-    if (!h.progressive && (!h.dc[h.comp[c].td].present || !h.ac[h.comp[c].ta].present))
+    if (!h.progressive && !h.multiscan && (!h.dc[h.comp[c].td].present || !h.ac[h.comp[c].ta].present))
       return fail(h, JH_CORRUPT, "missing Huffman table");
   }
   // colour space guess (libjpeg jdapimin.c default_decompress_parms)

@@ -417,6 +417,18 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     jpeg_cmyk_ = v != 0;
     return DG_OK;
   }
+  if (k == "jpeg_multiscan") {
+    // Three-component sequential JPEGs whose scans carry one or two components
+    // each (non-interleaved; default off: DG_ERR_UNSUPPORTED "non-interleaved
+    // multi-scan JPEG").  1: parse_jpeg_header walks their scans, every scan
+    // becomes an entropy-only descriptor behind the batch's images and the
+    // batch's k_huff_write runs its multiscan instantiation, which stores each
+    // scan's blocks in the image's MCU-interleaved order (ms_index, dg_types.h).
+    // dg_probe keeps describing the default options.
+    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
+    jpeg_multiscan_ = v != 0;
+    return DG_OK;
+  }
   if (k == "resize16") {
     // 16-bit PNGs that are not their bucket's size (default off:
     // DG_ERR_UNSUPPORTED).  1, together with "png16": they resize with the
@@ -1432,7 +1444,8 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
       p.status = DG_ERR_CORRUPT;
       return DG_OK;
     }
-    parse_jpeg_header(h, len, p.hdr, jpeg_h1v2_, jpeg_cmyk_);  // options "jpeg_h1v2", "jpeg_cmyk"
+    // options "jpeg_h1v2", "jpeg_cmyk", "jpeg_multiscan"
+    parse_jpeg_header(h, len, p.hdr, jpeg_h1v2_, jpeg_cmyk_, jpeg_multiscan_);
     if (p.hdr.status != JH_OK) {
       p.status = p.hdr.status == JH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
       return DG_OK;
@@ -1847,11 +1860,14 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   if (next()) return DG_ERR_DEVICE;
   launch_huff_scan(sl.st, dm, lst(L_SCAN), cnt(L_SCAN), subs, b.nc4);
   if (next()) return DG_ERR_DEVICE;
+  // multiscan parents: every padding block cleared, in front of the write pass on the same stream, which
+  // stores over those an interleaved scan codes
+  launch_ms_zero(sl.st, dd, lst(L_MS_ZERO), cnt(L_MS_ZERO));
   if (b.stage_on)
     launch_huff_scatter(sl.st, dd, lst(L_HUFF), cnt(L_HUFF), subs);
   else
     launch_huff_write(sl.st, dm, lst(L_HUFF), cnt(L_HUFF), hp, subs, fl, b.max_slots, qp, (uint32_t)write_pair_, ck,
-                      b.nc4);
+                      b.nc4, b.ms);
   if (next()) return DG_ERR_DEVICE;
   if (next()) return DG_ERR_DEVICE;  // coeffs (side stream)
   if (pside || dc_side) HIPCHK(hipStreamWaitEvent(sl.st, sl.ev_prog, 0));  // progressive coefficients
@@ -2112,6 +2128,10 @@ dg_status Context::finish_body(Slot &sl) {
   for (int i = 0; i < b.n; i++) {
     if (b.desc_of[i] < 0) continue;
     int status = back[b.desc_of[i]].status;
+    // a multiscan image takes its scan descriptors' status (truncated data, a write mismatch): corrupt first
+    if (back[b.desc_of[i]].ms.role == kMsParent)
+      for (const Batch::MsScan &ms : b.ms_scans)
+        if (ms.parent == b.desc_of[i] && back[ms.desc].status > status) status = back[ms.desc].status;
     if (back[b.desc_of[i]].fmt == kFmtPng && back[b.desc_of[i]].png.nchunks) {
       stat_png_chunks_ += back[b.desc_of[i]].png.nchunks;
       stat_png_serial_ += back[b.desc_of[i]].png.serial ? 1 : 0;

@@ -100,6 +100,15 @@ struct Batch {
   // the batch holds a four-component JPEG (option "jpeg_cmyk"): its entropy passes run their NC = 4
   // instantiations (checkpoint records CkptN<4>), and sync2 / entropy_once / idct_fused stand down
   bool nc4 = false;
+  // the batch holds a non-interleaved baseline JPEG (option "jpeg_multiscan"): descs holds, behind the images'
+  // descriptors, one entropy-only descriptor per scan of such an image (ms_scans); k_huff_write runs its
+  // multiscan instantiation, and entropy_once / idct_fused stand down
+  bool ms = false;
+  struct MsScan {
+    int desc, parent;  // descriptor indices
+    int image, scan;   // the image and its scan (JpegHeader::scans)
+  };
+  std::vector<MsScan> ms_scans;
   uint32_t max_slots = 1; // largest Huffman table count of an image (dynamic LDS of k_huff_sync/fix)
   uint32_t max_ac = 0;    // most distinct AC tables of a baseline JPEG (k_huff_sync multi-symbol lookups)
   size_t words_off = 0, words_bytes = 0;  // contiguous encoder bit buffers (zeroed per batch)
@@ -194,6 +203,7 @@ enum ListId {
   L_PENC_ROW16,                                             // PNG re-encode of 16-bit samples: filter rows (k_penc_filter16)
   L_DESTUFF_WG,                                             // every kDsWgChunks-th destuff chunk (k_destuff_count / _write)
   L_CMYK,                                                   // four planes -> RGB of a CMYK / YCCK JPEG (k_cmyk)
+  L_MS_ZERO,                                                // multiscan parents: blocks no scan codes (k_ms_zero)
   L_COUNT
 };
 static_assert((int)L_COUNT <= 48, "Batch::lists");
@@ -262,6 +272,8 @@ class Context {
   void layout_png(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  void layout_entropy_stream(size_t scan_len, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  void layout_scan(int i, int j, Batch &b, BatchLayout &bl);
   int plan_resize(const ImagePlan &p, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   int plan_resize16(const ImagePlan &p, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_output_and_encode(const SubmitArgs &a, int i, int last_stage, Batch &b, BatchLayout &bl, ImageDesc &d,
@@ -532,6 +544,7 @@ class Context {
   bool png16_ = false;                  // option "png16": 16-bit PNGs decode on the GPU
   bool jpeg_h1v2_ = false;              // option "jpeg_h1v2": 4:4:0-style JPEGs decode on the GPU
   bool jpeg_cmyk_ = false;              // option "jpeg_cmyk": Adobe CMYK / YCCK JPEGs decode on the GPU (to RGB)
+  bool jpeg_multiscan_ = false;         // option "jpeg_multiscan": non-interleaved baseline JPEGs decode on the GPU
   bool resize16_ = false;               // option "resize16": ... and resize to their bucket (dg_resize16.hip)
   bool penc16_ = false;                 // option "penc16": ... and go into the PNG re-encoder as 16-bit samples (dg_penc16.h)
   bool penc_dynamic_ = false;           // option "penc_dynamic": PNG re-encode with per-image Huffman codes where shorter

@@ -340,7 +340,7 @@ dg_status Context::pool_tables(Batch &b) {
     // (planning may run on pool threads; dg_last_error is the caller's)
     if (p.status == DG_ERR_UNSUPPORTED && p.fmt == kFmtPng && p.png.depth == 16) set_error(p.png.why);
     if (p.status || p.fmt != kFmtJpeg) continue;
-    hneed += p.hdr.progressive ? p.hdr.tables.size() : 2u * (size_t)p.hdr.ncomp;
+    hneed += (p.hdr.progressive || p.hdr.multiscan) ? p.hdr.tables.size() : 2u * (size_t)p.hdr.ncomp;
     qneed += (size_t)p.hdr.ncomp;
   }
   if (hpool_.size() > kPoolKeep || qpool_.size() > kPoolKeep ||
@@ -353,7 +353,7 @@ dg_status Context::pool_tables(Batch &b) {
     if (p.status || p.fmt != kFmtJpeg) continue;
     int worst = 0;  // -1: a table that does not build (corrupt), -2: pools full for this batch
     auto use = [&](int idx) { worst = std::min(worst, idx); };
-    if (p.hdr.progressive) {  // the tables each scan uses
+    if (p.hdr.progressive || p.hdr.multiscan) {  // the tables each scan uses
       for (const HuffSpec &t : p.hdr.tables) use(pool_huff(t));
       for (int c = 0; c < p.hdr.ncomp; c++) use(pool_quant(p.hdr.q[p.hdr.comp[c].tq]));
     } else {
@@ -419,6 +419,10 @@ void Context::layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl) {
   // instantiations; the paths that keep three DC sums (sync2, entropy_once, idct_fused) stand down for it
   for (int i = 0; i < a.n; i++)
     if (!b.plans[i].status && b.plans[i].fmt == kFmtJpeg && b.plans[i].hdr.ncomp == 4) b.nc4 = true;
+  // a non-interleaved baseline JPEG (option "jpeg_multiscan") puts the batch on k_huff_write's multiscan
+  // instantiation; entropy_once and idct_fused stand down for it
+  for (int i = 0; i < a.n; i++)
+    if (!b.plans[i].status && b.plans[i].fmt == kFmtJpeg && b.plans[i].hdr.multiscan) b.ms = true;
   for (int i = 0; i < a.n; i++) {
     const ImagePlan &p = b.plans[i];
     if (p.status) continue;
@@ -440,6 +444,71 @@ void Context::layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl) {
     b.descs.push_back(d);
     bl.offs.push_back(o);
   }
+  // the scan descriptors of multiscan images, behind every image's descriptor (image index order and
+  // descriptor index order still agree for real images)
+  for (int i = 0; b.ms && i < a.n; i++) {
+    const ImagePlan &p = b.plans[i];
+    if (p.status || p.fmt != kFmtJpeg || !p.hdr.multiscan) continue;
+    for (int j = 0; j < (int)p.hdr.scans.size(); j++) layout_scan(i, j, b, bl);
+  }
+}
+
+// The entropy-only descriptor of scan j of multiscan image i (ScanMap, dg_types.h): a stream of its own with
+// its own subsequences, tables and restart interval, decoded in the scan's own block order.
+void Context::layout_scan(int i, int j, Batch &b, BatchLayout &bl) {
+  const JpegHeader &h = b.plans[i].hdr;
+  const JpegScan &sc = h.scans[j];
+  const ImageDesc &par = b.descs[b.desc_of[i]];
+  ImageDesc d;
+  memset(&d, 0, sizeof(d));
+  Offs o;
+  memset(&o, 0, sizeof(o));
+  for (int s_ = 0; s_ < kStages; s_++) o.pass_cache[s_] = -1;
+  d.fmt = kFmtJpeg;
+  d.sample_bytes = 1;
+  d.ncomp = (uint8_t)sc.ns;
+  d.sem = par.sem;
+  d.ckpt = ckpt_ ? 1u : 0u;
+  d.ms = ms_scan_map(par, (uint32_t)sc.ns, sc.comp, d.total_blocks);
+  uint32_t bpm = 0;
+  for (int q = 0; q < sc.ns; q++) {  // the scan's components, numbered in scan order
+    const int c = sc.comp[q];
+    d.ch[q] = par.ch[c];
+    d.cv[q] = par.cv[c];
+    d.cfirst[q] = bpm;
+    const uint32_t nb = sc.ns == 1 ? 1u : par.ch[c] * par.cv[c];
+    for (uint32_t k = 0; k < nb; k++) d.blk_comp[bpm + k] = (uint8_t)q;
+    bpm += nb;
+  }
+  d.bpm = bpm;
+  for (uint32_t k = 0; k < bpm; k++) d.comp_bits |= (uint32_t)d.blk_comp[k] << (2 * k);
+  if (sc.ns > 1) {
+    d.mcux = par.mcux;
+    d.mcuy = par.mcuy;
+  }
+  d.restart = (uint32_t)sc.restart;  // in the scan's own MCUs: blocks for a one-component scan
+  d.blocks_per_seg = d.restart * bpm;
+  int nslots = 0;
+  auto slot_of = [&](int pidx) {
+    for (int s = 0; s < nslots; s++)
+      if (d.hslot[s] == pidx) return s;
+    d.hslot[nslots] = (uint16_t)pidx;
+    return nslots++;
+  };
+  uint32_t acs = 0;
+  for (int q = 0; q < sc.ns; q++) {
+    d.slotmap |= (uint32_t)slot_of(pool_huff(h.tables[sc.dc_tab[q]])) << ((2 * q) * 4);
+    const int as = slot_of(pool_huff(h.tables[sc.ac_tabs[q]]));
+    d.slotmap |= (uint32_t)as << ((2 * q + 1) * 4);
+    acs |= 1u << as;
+  }
+  d.nslots = (uint8_t)nslots;
+  b.max_slots = std::max<uint32_t>(b.max_slots, (uint32_t)nslots);
+  b.max_ac = std::max<uint32_t>(b.max_ac, std::min<uint32_t>((uint32_t)__builtin_popcount(acs), kMultiLuts));
+  layout_entropy_stream(sc.end - sc.off, b, bl, d, o);
+  b.ms_scans.push_back({(int)b.descs.size(), b.desc_of[i], i, j});
+  b.descs.push_back(d);
+  bl.offs.push_back(o);
 }
 
 void Context::layout_png(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
@@ -567,7 +636,7 @@ void Context::layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl,
   };
   d.slotmap = 0;
   for (int c = 0; c < h.ncomp; c++) {
-    if (!h.progressive) {
+    if (!h.progressive && !h.multiscan) {  // (a multiscan image's scan descriptors hold its tables)
       d.slotmap |= (uint32_t)slot_of(pool_huff(h.dc[h.comp[c].td])) << ((2 * c) * 4);
       d.slotmap |= (uint32_t)slot_of(pool_huff(h.ac[h.comp[c].ta])) << ((2 * c + 1) * 4);
     }
@@ -575,13 +644,17 @@ void Context::layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl,
   }
   d.nslots = (uint8_t)nslots;
   b.max_slots = std::max<uint32_t>(b.max_slots, (uint32_t)nslots);
-  if (!h.progressive) {  // distinct AC slots (k_huff_sync builds a multi-symbol lookup for each, up to 3)
+  // distinct AC slots (k_huff_sync builds a multi-symbol lookup for each, up to 3)
+  if (!h.progressive && !h.multiscan) {
     uint32_t acs = 0;
     for (int c = 0; c < h.ncomp; c++) acs |= 1u << ((d.slotmap >> ((2 * c + 1) * 4)) & 15u);
     b.max_ac = std::max<uint32_t>(b.max_ac, std::min<uint32_t>((uint32_t)__builtin_popcount(acs), kMultiLuts));
   }
   if (h.progressive) {  // scans decoded by k_prog_scan (records built once the source address is known)
     d.prog = (uint32_t)h.scans.size();
+    if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
+  } else if (h.multiscan) {  // the parent of its scans' descriptors (layout_scan): no entropy stream of its own
+    d.ms.role = kMsParent;
     if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
   } else {
     layout_entropy(a, i, b, bl, d, o);
@@ -591,7 +664,7 @@ void Context::layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl,
   // sparse blocks: k_huff_write's cooperative flush + k_idct_t only (not the
   // fused / decode-once writers, k_idct or k_band_dec; progressive scans
   // write whole blocks)
-  o.ccnt = (sparse_coef_ && idct_thread_ && !d.prog && !d.idct_fused && !(entropy_once_ && !b.nc4))
+  o.ccnt = (sparse_coef_ && idct_thread_ && !d.prog && !d.idct_fused && !(entropy_once_ && !b.nc4 && !b.ms))
                ? bl.CO.take((size_t)d.total_blocks, 64) + 1
                : 0;
   for (int c = 0; c < 4; c++) o.plane[c] = (size_t)-1;  // allocated after the pass plan (not for k_band_dec)
@@ -602,9 +675,16 @@ void Context::layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl,
 // The entropy data of a baseline (sequential) JPEG: subsequences, checkpoints, destuff buffers.
 void Context::layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
   const JpegHeader &h = b.plans[i].hdr;
+  layout_entropy_stream(h.scan_end - h.scan_off, b, bl, d, o);
+  if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
+}
+
+// ... of one entropy stream of scan_len bytes: an image's single scan, or a scan descriptor's (layout_scan)
+void Context::layout_entropy_stream(size_t scan_len, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
   const uint32_t sub_bits = bl.sub_bits;
-  const bool once = entropy_once_ && !b.nc4;  // (a batch with a four-component image: the default write pass)
-  d.scan_len = (uint32_t)(h.scan_end - h.scan_off);
+  // (a batch with a four-component or a multiscan image: the default write pass)
+  const bool once = entropy_once_ && !b.nc4 && !b.ms;
+  d.scan_len = (uint32_t)scan_len;
   // Per-image subsequence size (option "sub_density" T > 0): a lane's
   // decode time follows its symbols and blocks, not its bits, so images
   // with few coded bits per block (flat, low quality: short EOB-heavy
@@ -621,11 +701,11 @@ void Context::layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &
   }
   // completed blocks go straight to plane pixels inside k_huff_write (not
   // with decode-once staging, whose k_huff_scatter writes coefficients)
-  d.idct_fused = (idct_fused_ && !once && !b.nc4) ? 1u : 0u;
+  d.idct_fused = (idct_fused_ && !once && !b.nc4 && !b.ms) ? 1u : 0u;
   // k_huff_write splits each range at the sync pass's half-way checkpoint
   // (option "write_split"): needs that checkpoint, no restart markers and
   // the plain write path
-  if (write_split_ && d.ckpt && !d.idct_fused && !once && h.restart == 0 && d.sub_bits >= 1024 &&
+  if (write_split_ && d.ckpt && !d.idct_fused && !once && d.restart == 0 && d.sub_bits >= 1024 &&
       d.sub_bits / 2 / kCkptBits - 1 < num_ckpt(d.sub_bits))
     d.ckpt |= 2u;
   if (d.idct_fused) b.any_fused = true;
@@ -646,7 +726,7 @@ void Context::layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &
   d.ckpt_base = (uint32_t)bl.ckpt_total;
   bl.ckpt_total += (uint64_t)d.nsub * num_ckpt(d.sub_bits);
   d.nchunk = std::max<uint32_t>(1, (d.scan_len + kDestuffChunk - 1) / kDestuffChunk);
-  uint32_t mcus = h.ncomp == 1 ? d.total_blocks : d.mcux * d.mcuy;
+  const uint32_t mcus = d.total_blocks / d.bpm;
   d.mk_cap = (d.restart ? mcus / d.restart + 2 : 0) + 64;
   d.ds_lsw = 0;
   while ((32u << d.ds_lsw) < d.sub_bits) d.ds_lsw++;
@@ -658,7 +738,6 @@ void Context::layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &
   }
   o.mk = bl.L.take((size_t)d.mk_cap * 4, 16);
   o.chunk = bl.L.take((size_t)d.nchunk * 16, 16);
-  if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
 }
 
 // The pass plan (image_processing.rs:264-325), the alpha programs around it and the JPEG
@@ -1130,6 +1209,18 @@ void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const Bat
       patch_jpeg(b.plans[i].hdr, src, sl, o, b.desc_of[i], b);
     patch_passes(S, o, b.desc_of[i], b);
   }
+  for (const Batch::MsScan &ms : b.ms_scans) {  // scan descriptors: a stream inside the parent's source, its buffers
+    ImageDesc &d = b.descs[ms.desc];
+    const Offs &o = bl.offs[ms.desc];
+    const ImageDesc &par = b.descs[ms.parent];
+    const uint8_t *src = a.host_io ? (const uint8_t *)sl.input.p + bl.in_off[ms.image] : a.d_srcs[ms.image];
+    d.scan = (uint64_t)(uintptr_t)(src + b.plans[ms.image].hdr.scans[ms.scan].off);
+    d.coef = par.coef;
+    d.ccnt = par.ccnt;
+    d.ds = (uint64_t)(uintptr_t)(S + o.ds);
+    d.mk = (uint64_t)(uintptr_t)(S + o.mk);
+    d.chunk = (uint64_t)(uintptr_t)(S + o.chunk);
+  }
 }
 
 void Context::patch_jpeg(const JpegHeader &h, const uint8_t *src, const Slot &sl, const Offs &o, int di, Batch &b) {
@@ -1140,7 +1231,7 @@ void Context::patch_jpeg(const JpegHeader &h, const uint8_t *src, const Slot &sl
   d.ccnt = (o.ccnt && !(d.pass[0].mode & kHDecode)) ? (uint64_t)(uintptr_t)((char *)sl.coef.p + o.ccnt - 1) : 0;
   if (d.prog) {
     prog_scan_records(h, src, di, b);
-  } else {
+  } else if (d.ms.role != kMsParent) {
     d.ds = (uint64_t)(uintptr_t)(S + o.ds);
     d.stage = d.stage_cap ? (uint64_t)(uintptr_t)(S + o.stage) : 0;
     d.mk = (uint64_t)(uintptr_t)(S + o.mk);
@@ -1329,6 +1420,20 @@ void Context::build_lists(Batch &b) {
 void Context::image_items(int di, Batch &b, ClassLists &cl) {
   const ImageDesc &d = b.descs[di];
   const uint32_t I = (uint32_t)di;
+  auto entropy_items = [&]() {
+    // split ranges (write_split): 128 ranges per k_huff_write workgroup, two lanes each
+    const uint32_t wstep = (d.ckpt & 2u) ? kSubPerWg / 2 : kSubPerWg;
+    for (uint32_t w = 0; w < d.nsub; w += wstep) b.lists[L_HUFF].push_back({I, w});
+    for (uint32_t w = 0; w < d.nsub; w += kSubPerWg - 1) b.lists[L_SYNC].push_back({I, w});
+    b.descs[di].ds_state0 = (uint32_t)b.lists[L_DESTUFF].size();  // k_destuff_one's state words, list order
+    for (uint32_t c = 0; c < d.nchunk; c++) b.lists[L_DESTUFF].push_back({I, c});
+    for (uint32_t c = 0; c < d.nchunk; c += kDsWgChunks) b.lists[L_DESTUFF_WG].push_back({I, c});
+    b.lists[L_SCAN].push_back({I, 0});
+  };
+  if (d.ms.role == kMsScan) {  // a multiscan image's scan: the entropy passes only
+    entropy_items();
+    return;
+  }
   for (uint32_t k = 0; k < kAlphaPoints; k++)
     if (d.aop[k].prog) {
       const uint32_t cnt = d.aop[k].width * d.aop[k].rows;
@@ -1348,15 +1453,10 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
     if (d.prog) {
       const uint64_t bytes = (uint64_t)d.total_blocks * 128;
       for (uint32_t c = 0; (uint64_t)c * kProgZeroBytes < bytes; c++) b.lists[L_PROG_ZERO].push_back({I, c});
+    } else if (d.ms.role == kMsParent) {  // its scan descriptors decode; k_ms_zero clears what no scan codes
+      b.lists[L_MS_ZERO].push_back({I, 0});
     } else {
-      // split ranges (write_split): 128 ranges per k_huff_write workgroup, two lanes each
-      const uint32_t wstep = (d.ckpt & 2u) ? kSubPerWg / 2 : kSubPerWg;
-      for (uint32_t w = 0; w < d.nsub; w += wstep) b.lists[L_HUFF].push_back({I, w});
-      for (uint32_t w = 0; w < d.nsub; w += kSubPerWg - 1) b.lists[L_SYNC].push_back({I, w});
-      b.descs[di].ds_state0 = (uint32_t)b.lists[L_DESTUFF].size();  // k_destuff_one's state words, list order
-      for (uint32_t c = 0; c < d.nchunk; c++) b.lists[L_DESTUFF].push_back({I, c});
-      for (uint32_t c = 0; c < d.nchunk; c += kDsWgChunks) b.lists[L_DESTUFF_WG].push_back({I, c});
-      b.lists[L_SCAN].push_back({I, 0});
+      entropy_items();
     }
     uint32_t items = 0;
     for (uint32_t c = 0; c < d.ncomp; c++) items += d.cbh[c] * ((d.cbw[c] + 63) / 64);  // kIdctBlocks

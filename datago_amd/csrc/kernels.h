@@ -34,7 +34,11 @@ void launch_huff_scan(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint3
                       bool nc4 = false);
 void launch_huff_write(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                        const HuffTable *pool, const SubState *subs, BatchFlags *flags, uint32_t max_slots,
-                       const QuantTable *qpool, uint32_t pair, const Ckpt *ckpt, bool nc4 = false);
+                       const QuantTable *qpool, uint32_t pair, const Ckpt *ckpt, bool nc4 = false, bool ms = false);
+// ms: the batch holds a non-interleaved baseline image (option "jpeg_multiscan"): k_huff_write's instantiation
+// that maps a scan descriptor's blocks into its parent's buffer; k_ms_zero (one workgroup per parent) clears the
+// blocks of that buffer no scan codes
+void launch_ms_zero(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // fused IDCT leftovers (BatchFlags::idct_list), grid-strided over the device-side count
 void launch_idct_list(hipStream_t st, const ImageDesc *imgs, const QuantTable *qpool, const BatchFlags *flags,
                       uint32_t nwg);

@@ -918,7 +918,9 @@ __global__ __launch_bounds__(256) void k_huff_scan4(ImageDesc *__restrict__ imgs
 // 1-4 did, in 32 instead of 36 KiB per workgroup (three workgroups per CU).
 constexpr int kBlkStride = 64;
 
-template <int NC>
+// MS: the instantiation a batch with a non-interleaved baseline image runs (option "jpeg_multiscan"): the
+// blocks of its scan descriptors go through ms_index into the parent's MCU-interleaved buffer.
+template <int NC, bool MS = false>
 __global__ __launch_bounds__(256) void k_huff_write(ImageDesc *__restrict__ imgs,
                                                     const WgItem *__restrict__ list,
                                                     const HuffTable *__restrict__ pool,
@@ -1012,8 +1014,8 @@ __global__ __launch_bounds__(256) void k_huff_write(ImageDesc *__restrict__ imgs
       for (int i = 0; i < 8; i++) p[i] = zero;
     }
     RangeAccN<NC> acc;
-    decode_range<true, HuffTable, true>(im, tabs, gp<const uint8_t>(im.ds), gp<const uint32_t>(im.mk), s, in,
-                                        acc, &w, nullptr, false, 0, nullptr, nullptr, 0xFFu, pair, a0o, a1o);
+    decode_range<true, HuffTable, true, NC, MS>(im, tabs, gp<const uint8_t>(im.ds), gp<const uint32_t>(im.mk), s, in,
+                                                acc, &w, nullptr, false, 0, nullptr, nullptr, 0xFFu, pair, a0o, a1o);
     if (acc.out != want || (s == 0 && (flags->debug & kDbgForceWriteMismatch))) {
       // the write pass left this range in another state than the sync pass
       // proved: the blocks after it are not trustworthy.  The image goes back
@@ -1026,6 +1028,44 @@ __global__ __launch_bounds__(256) void k_huff_write(ImageDesc *__restrict__ imgs
   if (flags->wgtime) {
     __syncthreads();
     wg_time_store(flags, flags->wgtime_write + blockIdx.x, t_start);
+  }
+}
+
+// Non-interleaved baseline JPEG (option "jpeg_multiscan"): the padding blocks of the parent's MCU-interleaved
+// buffer -- the columns and rows between every component's own grid ceil(cdsw / 8) x ceil(cdsh / 8) and its
+// MCU-padded grid cbw x cbh -- are cleared: dense blocks are zeroed, sparse ones get mask 0.  A component with a
+// scan to itself has those blocks coded by no scan, and they must read as zero coefficients.  A component coded
+// in an interleaved scan has them in the file: this kernel clears them too (it does not know the scans), and
+// k_huff_write, launched after it on the same stream, stores what the scan codes over them.  So it must stay
+// in front of the write pass on that stream, never beside or behind it.
+// One workgroup per parent; at most (h - 1) columns and (v - 1) rows of blocks per component.
+__global__ __launch_bounds__(256) void k_ms_zero(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  const ImageDesc &im = imgs[list[blockIdx.x].image];
+  DG_GLOBAL u32x4 *coef = gp<u32x4>(im.coef);
+  DG_GLOBAL uint8_t *cnt = im.ccnt ? gp<uint8_t>(im.ccnt) : nullptr;
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+  for (uint32_t c = 0; c < im.ncomp; c++) {
+    const uint32_t gw = (im.cdsw[c] + 7) / 8, gh = (im.cdsh[c] + 7) / 8, bw = im.cbw[c], bh = im.cbh[c];
+    const uint32_t right = bw - gw, nr = right * gh, n = nr + (bh - gh) * bw;
+    const uint32_t lh = im.ch[c] >> 1, lv = im.cv[c] >> 1;  // log2 of 1, 2, 4
+    for (uint32_t k = threadIdx.x; k < n; k += 256) {
+      uint32_t by, bx;
+      if (k < nr) {
+        by = k / right;
+        bx = gw + (k - by * right);
+      } else {
+        by = gh + (k - nr) / bw;
+        bx = (k - nr) % bw;
+      }
+      const uint32_t idx = ms_block_index(im.mcux, im.bpm, im.cfirst[c], lh, lv, by, bx);
+      if (idx >= im.total_blocks) continue;
+      if (cnt) {
+        cnt[idx] = 0;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++) coef[(size_t)idx * 8 + i] = zero;
+      }
+    }
   }
 }
 
@@ -3610,14 +3650,24 @@ void launch_huff_scan(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint3
 }
 void launch_huff_write(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg,
                        const HuffTable *pool, const SubState *subs, BatchFlags *flags, uint32_t max_slots,
-                       const QuantTable *qpool, uint32_t pair, const Ckpt *ckpt, bool nc4) {
+                       const QuantTable *qpool, uint32_t pair, const Ckpt *ckpt, bool nc4, bool ms) {
   if (!nwg) return;
-  if (nc4)
-    hipLaunchKernelGGL(k_huff_write<4>, dim3(nwg), dim3(256), (size_t)max_slots * sizeof(HuffTable), st, imgs, list,
-                       pool, subs, flags, qpool, pair, ckpt);
+  const size_t lds = (size_t)max_slots * sizeof(HuffTable);
+  if (nc4 && ms)
+    hipLaunchKernelGGL((k_huff_write<4, true>), dim3(nwg), dim3(256), lds, st, imgs, list, pool, subs, flags, qpool,
+                       pair, ckpt);
+  else if (ms)  // a batch with a non-interleaved baseline image (option "jpeg_multiscan")
+    hipLaunchKernelGGL((k_huff_write<3, true>), dim3(nwg), dim3(256), lds, st, imgs, list, pool, subs, flags, qpool,
+                       pair, ckpt);
+  else if (nc4)
+    hipLaunchKernelGGL(k_huff_write<4>, dim3(nwg), dim3(256), lds, st, imgs, list, pool, subs, flags, qpool, pair,
+                       ckpt);
   else
-    hipLaunchKernelGGL(k_huff_write<3>, dim3(nwg), dim3(256), (size_t)max_slots * sizeof(HuffTable), st, imgs, list,
-                       pool, subs, flags, qpool, pair, ckpt);
+    hipLaunchKernelGGL(k_huff_write<3>, dim3(nwg), dim3(256), lds, st, imgs, list, pool, subs, flags, qpool, pair,
+                       ckpt);
+}
+void launch_ms_zero(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  DG_LAUNCH(k_ms_zero, nwg, st, imgs, list);
 }
 void launch_idct_list(hipStream_t st, const ImageDesc *imgs, const QuantTable *qpool, const BatchFlags *flags,
                       uint32_t nwg) {

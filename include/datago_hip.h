@@ -46,7 +46,8 @@ extern "C" {
 typedef enum dg_status {
   DG_OK = 0,
   DG_ERR_UNSUPPORTED = 1, /* valid image the GPU path does not decode (arithmetic, 12-bit,
-                             CMYK / YCCK unless option "jpeg_cmyk" is set, non-JPEG/PNG...;
+                             CMYK / YCCK unless option "jpeg_cmyk" is set, a non-interleaved
+                             baseline JPEG unless option "jpeg_multiscan" is set, non-JPEG/PNG...;
                              16-bit PNG unless option "png16" is set,
                              and then still one that needs the resize or an encoder unless
                              "resize16" / "penc16" are set too):
@@ -291,6 +292,27 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 hands CMYK back unconverted, so decode_semantics 0 takes the same last step on its own
  *                 planes (which equal 255 - Pillow's CMYK image).  ICC profiles are ignored, as the
  *                 reference ignores them.  Any other value: DG_ERR_INVALID
+ *   "jpeg_multiscan"  1 = decode non-interleaved baseline JPEGs: three-component SOF0 / SOF1 files whose
+ *                 scans carry one or two components each (what jpegtran -scans / cjpeg -scans and some
+ *                 scanner and camera firmwares write), on the parallel entropy path of single-scan files.
+ *                 Default 0: DG_ERR_UNSUPPORTED ("non-interleaved multi-scan JPEG"), as dg_probe's
+ *                 gpu_supported reports, which describes the default options.  With 1 such a file is
+ *                 accepted when its scans name disjoint component sets that cover every component once, in
+ *                 any order, each scan one or two components; the Huffman tables and the restart interval in
+ *                 force at each SOS are that scan's (a DHT under one id before every scan, a DRI between
+ *                 scans).  A file whose first scan names all components is parsed and decoded exactly as
+ *                 without the option.  DG_ERR_UNSUPPORTED, each with a dg_last_error text of its own: a
+ *                 component no scan codes before EOI, a DQT between scans that changes a table some
+ *                 component uses, a four-component frame (also with "jpeg_cmyk"), more scans than
+ *                 components, a sampling factor of 3.  DG_ERR_CORRUPT: a component coded twice, spectral
+ *                 selection or successive approximation other than 0 / 63 / 0 / 0, data that ends before
+ *                 every component was coded, a second frame header (SOFn) after a scan.  decode_semantics 0 returns libjpeg-turbo's pixels (bit-exact
+ *                 with Pillow).  decode_semantics 1 finishes the image over the MCU-padded grid with the
+ *                 blocks no scan codes (those between a component's own ceil(w / 8) x ceil(h / 8) grid and
+ *                 the padded grid, for a component with a scan to itself) as zero coefficients: zune-jpeg's
+ *                 zero-initialised coefficient storage, recalled from the crate's source and
+ *                 parity-unpinned like the rest of that mode.  A scan whose data is cut short fails its
+ *                 image alone (DG_ERR_CORRUPT).  Any other value: DG_ERR_INVALID
  *   "png16"       1 = decode 16-bit PNGs on the GPU (default 0: DG_ERR_UNSUPPORTED, as dg_probe's
  *                 gpu_supported reports, which describes the default options).  Colour types 0/2/4/6
  *                 become Luma16 / Rgb16 / LumaA16 / Rgba16 (a tRNS key adds a 16-bit alpha, 0 or
