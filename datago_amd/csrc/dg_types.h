@@ -176,7 +176,7 @@ constexpr uint32_t kHBandsDefault = 16;  // default ResizePass::bands (8 -> 16: 
 constexpr int kStages = 4;  // R1.H, R1.V, R2.H, R2.V
 
 // ---- PNG (ImageDesc::fmt == kFmtPng)
-constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1;
+constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1, kFmtGif = 2;
 // IDAT payloads are gathered into one contiguous zlib stream (k_png_gather),
 // inflated into filtered scanlines (k_png_inflate, one wave per image),
 // unfiltered (k_png_unfilter, one wave per 64-row band on a diagonal
@@ -202,6 +202,30 @@ struct PngDesc {
   uint32_t rawlen;    // inflated bytes expected
   uint32_t uf_flag0;  // k_png_unfilter: first band progress flag of this image
 };
+
+// ---- GIF (ImageDesc::fmt == kFmtGif, option "gif"): the first frame on the logical screen as Rgba8.
+// The frame's data sub-blocks are one LZW code stream: read through the chain where every block but
+// the last holds 255 bytes (blocked), else gathered into a contiguous copy first (k_gif_gather).
+// k_gif_lzw (one wave per image, dg_gif.h) decodes it into the fw x fh index plane in stream row order;
+// k_gif_expand looks the indices up in the folded RGBA palette and places them on the screen
+// (de-interlace, frame offset, clipping, transparent black outside the frame).  Anything irregular
+// sets ImageDesc::status = DG_ERR_UNSUPPORTED and GifDesc::fail names it.
+struct GifDesc {
+  uint64_t src;       // blocked: the first sub-block's length byte in the file; else the gathered code bytes
+  uint64_t src_end;   // one past the last source byte the stream occupies (loads stay below it)
+  uint64_t idx;       // index plane: fw x fh bytes, rows in stream order
+  uint64_t pal;       // 256 x RGBA palette (device)
+  uint32_t nbytes;    // LZW code bytes
+  uint32_t blocked;   // 1: code byte k is src[1 + k + k / 255]
+  uint32_t mcs;       // LZW minimum code size (2..8)
+  uint32_t npal;      // entries of the colour table in use
+  uint32_t left, top, fw, fh;  // the frame's rectangle on the screen
+  uint32_t interlace;
+  uint32_t fail;      // kGifFail*: written by k_gif_lzw / k_gif_expand
+};
+constexpr uint32_t kGifFailCode = 1;     // a code above the next free one, or the next free one straight after a clear
+constexpr uint32_t kGifFailShort = 2;    // the data ends (or an end code comes) before fw x fh indices
+constexpr uint32_t kGifFailPalette = 3;  // an index at or past the colour table's size
 
 // Adam7 pass p of a W x H image (PNG spec 8.2): origin (x0, y0), spacing (dx, dy)
 DG_HD uint32_t png_a7(uint32_t p, uint32_t k) {
@@ -266,10 +290,12 @@ struct InfChunk {
   uint32_t span;      // compressed bytes per chunk of this image
 };
 constexpr uint32_t kInfTabBytes = 4096;        // per-chunk table scratch (see k_inf_decode)
-// A gather job: copy `len` bytes (one IDAT payload) from src to dst.
+// A gather job: copy `len` bytes (one IDAT payload) from src to dst.  With count != 0 a run of a GIF's
+// sub-block chain (k_gif_gather): `count` blocks of `len` data bytes, each behind its length byte, from src
+// (the first length byte) to len * count contiguous bytes at dst.
 struct GatherJob {
   uint64_t src, dst;
-  uint32_t len, pad;
+  uint32_t len, count;
 };
 constexpr uint32_t kGatherPiece = 16384;  // bytes per gather workgroup
 
@@ -434,7 +460,7 @@ struct ImageDesc {
   uint32_t final_src_c;
   uint32_t color_fused;     // 1: pass[0] converts colour itself, pix is never written
   // ---- format, PNG, alpha handling, final conversion
-  uint32_t fmt;             // kFmtJpeg / kFmtPng
+  uint32_t fmt;             // kFmtJpeg / kFmtPng / kFmtGif
   uint32_t prog;            // progressive JPEG: scans decoded by k_prog_scan (0: sequential)
   uint32_t crec;            // bit c: component c's plane holds chroma records (dg_plane.h; option "chroma_rec")
   uint32_t copy_mode;       // k_copy: 0 same channels, 1 L->RGB, 2 RGBA->RGB blend over gray,
@@ -443,7 +469,10 @@ struct ImageDesc {
                             // 5 16-bit samples, same channels, 6 16-bit L / LA / RGB / RGBA -> RGB8
                             // ((v + 128) / 257 per sample, luma replicated, alpha dropped)
   uint32_t sample_bytes;    // bytes per sample of the decoded image and, unless copy_mode 6, of the output: 1 or 2
-  PngDesc png;
+  union {
+    PngDesc png;            // fmt == kFmtPng
+    GifDesc gif;            // fmt == kFmtGif
+  };
   AlphaOp aop[kAlphaPoints];
   EncDesc enc;
   ScanMap ms;               // option "jpeg_multiscan": the parent of scan descriptors, or one of them

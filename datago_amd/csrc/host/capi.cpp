@@ -212,6 +212,23 @@ dg_status dg_probe(const uint8_t *bytes, size_t len, dg_probe_info *out) {
     }
     return DG_OK;
   }
+  if (dg::is_gif(bytes, len)) {
+    dg::GifHeader h;
+    dg::parse_gif_header(bytes, len, h);
+    out->format = DG_FMT_GIF;
+    out->width = h.width;    // the logical screen
+    out->height = h.height;
+    out->components = 4;     // Rgba8: the first frame composited on the screen
+    out->bit_depth = 8;
+    out->precision = 8;
+    out->progressive = h.interlace;
+    out->gpu_supported = 0;  // the default options (option "gif" decodes it)
+    if (h.status == dg::GH_CORRUPT) {
+      dg::set_error(h.why);
+      return DG_ERR_CORRUPT;
+    }
+    return DG_OK;
+  }
   if (!dg::is_jpeg(bytes, len)) {
     dg::set_error("unknown image format");
     return DG_ERR_CORRUPT;

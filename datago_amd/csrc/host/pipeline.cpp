@@ -395,6 +395,18 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     png16_ = v != 0;
     return DG_OK;
   }
+  if (k == "gif") {
+    // GIF87a / GIF89a files on the GPU (default off: DG_ERR_CORRUPT like any
+    // format the library does not know).  1: plan_image takes a GIF, its first
+    // frame is LZW-decoded by k_gif_lzw and composited on the logical screen as
+    // Rgba8 by k_gif_expand (dg_gif.hip), what image 0.25's GifDecoder returns
+    // for load_from_memory; from there it is an RGBA8 PNG's pixels.  Stream
+    // irregularities come back DG_ERR_UNSUPPORTED with a dg_last_error text.
+    // dg_probe names a GIF either way and keeps describing the default options.
+    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
+    gif_ = v != 0;
+    return DG_OK;
+  }
   if (k == "jpeg_h1v2") {
     // Colour JPEGs with a component at the full horizontal and half the
     // vertical rate (4:4:0, what a lossless 90-degree rotation makes of 4:2:2;
@@ -1439,6 +1451,23 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     W = p.png.width;
     H = p.png.height;
     C = (uint32_t)p.png.out_c;
+  } else if (gif_ && is_gif(h, len)) {  // option "gif"
+    p.fmt = kFmtGif;
+    parse_gif_header(h, len, p.gif);
+    if (p.gif.status != GH_OK) {
+      p.status = p.gif.status == GH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
+      return DG_OK;
+    }
+    // the working set (code bytes, index plane, Rgba8 screen) stays 32-bit addressable, as the PNG path's
+    if ((uint64_t)p.gif.width * p.gif.height * 4ull >= (1ull << 31) || (uint64_t)p.gif.fw * p.gif.fh >= (1ull << 31) ||
+        p.gif.nbytes >= (1ull << 28)) {
+      p.gif.why = "GIF: image too large for the GPU path";
+      p.status = DG_ERR_UNSUPPORTED;
+      return DG_OK;
+    }
+    W = p.gif.width;
+    H = p.gif.height;
+    C = 4;
   } else {
     if (!is_jpeg(h, len)) {
       p.status = DG_ERR_CORRUPT;
@@ -1541,7 +1570,8 @@ dg_status Context::output_size(const uint8_t *bytes, size_t len, int32_t forced,
   ImagePlan p;
   plan_image(bytes, len, forced, p);
   *nbytes = p.out_bytes;
-  if (p.status) set_error(p.fmt == kFmtPng ? p.png.why : (p.hdr.why ? p.hdr.why : "unsupported"));
+  if (p.status)
+    set_error(p.fmt == kFmtPng ? p.png.why : p.fmt == kFmtGif ? p.gif.why : (p.hdr.why ? p.hdr.why : "unsupported"));
   return (dg_status)p.status;
 }
 
@@ -1780,7 +1810,12 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
       launch_png_inflate(sl.st, dm, lst(L_PNG), cnt(L_PNG), 2, fl, ncu_);  // serial: every stream
     }
   }
+  if (!from_fix && b.any_gif) {  // GIF: code stream -> index plane (the entropy stage of these images)
+    launch_gif_gather(sl.st, (const GatherJob *)(M + b.gjob_off), lst(L_GIF_GATHER), cnt(L_GIF_GATHER));
+    launch_gif_lzw(sl.st, dm, lst(L_GIF_LZW), cnt(L_GIF_LZW));
+  }
   if (next()) return DG_ERR_DEVICE;
+  if (!from_fix && b.any_gif) launch_gif_expand(sl.st, dm, lst(L_GIF_EXPAND), cnt(L_GIF_EXPAND));
   if (!from_fix && b.any_png) {
     if (b.uf_n) {
       uint32_t *uf = (uint32_t *)((char *)sl.scratch.p + b.uf_flags_off);
@@ -2140,6 +2175,13 @@ dg_status Context::finish_body(Slot &sl) {
     }
     if (!status && b.unsettled && b.plans[i].fmt == kFmtJpeg && !b.plans[i].hdr.progressive)
       status = DG_ERR_UNSUPPORTED;
+    if (status && back[b.desc_of[i]].fmt == kFmtGif) {  // what k_gif_lzw / k_gif_expand met in the stream
+      const uint32_t f = back[b.desc_of[i]].gif.fail;
+      set_error(f == kGifFailCode    ? "GIF: LZW code above the next free code"
+                : f == kGifFailShort ? "GIF: image data ends before the frame is complete"
+                : f == kGifFailPalette ? "GIF: pixel index past the colour table"
+                                       : "GIF: decode failed");
+    }
     if (status) b.mptr[i]->status = status;
     if (b.plans[i].encode) {
       const uint32_t nb = back[b.desc_of[i]].enc.enc_bytes;

@@ -15,6 +15,7 @@
 #include "../dg_resize16.h"
 #include "buckets.h"
 #include "jpeg_header.h"
+#include "gif_header.h"
 #include "png_header.h"
 #include "jpeg_enc.h"
 #include "host_pool.h"
@@ -37,6 +38,7 @@ struct ImagePlan {
   uint32_t fmt = kFmtJpeg;
   JpegHeader hdr;
   PngHeader png;
+  GifHeader gif;  // fmt == kFmtGif (option "gif")
   int bucket = -1;
   uint32_t out_w = 0, out_h = 0, out_c = 0;
   uint64_t out_bytes = 0;
@@ -90,6 +92,7 @@ struct Batch {
   std::vector<uint8_t> blob;
   size_t blob_off = 0;
   bool any_png = false, any_alpha = false, any_enc = false;
+  bool any_gif = false;   // a GIF (option "gif"): k_gif_gather, k_gif_lzw, k_gif_expand
   bool penc_dyn = false;  // a PNG re-encode with option "penc_dynamic": histogram, k_penc_tree, dynamic count / write
   bool jenc_opt = false;  // a JPEG re-encode with option "jenc_optimize": k_enc_hist, k_enc_tree, per-image tables
   bool any_fused = false;  // some image's IDCT runs inside k_huff_write
@@ -204,6 +207,7 @@ enum ListId {
   L_DESTUFF_WG,                                             // every kDsWgChunks-th destuff chunk (k_destuff_count / _write)
   L_CMYK,                                                   // four planes -> RGB of a CMYK / YCCK JPEG (k_cmyk)
   L_MS_ZERO,                                                // multiscan parents: blocks no scan codes (k_ms_zero)
+  L_GIF_GATHER, L_GIF_LZW, L_GIF_EXPAND,                    // GIF decode (dg_gif.hip)
   L_COUNT
 };
 static_assert((int)L_COUNT <= 48, "Batch::lists");
@@ -270,6 +274,7 @@ class Context {
   void choose_sub_bits(const Batch &b, BatchLayout &bl);
   void layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl);  // per image: the next five
   void layout_png(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  void layout_gif(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_entropy_stream(size_t scan_len, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
@@ -542,6 +547,7 @@ class Context {
   bool idct_fused_ = false;             // option "idct_fused" (measured 7x slower k_huff_write: off)
   bool progressive_ = true;             // option "progressive"
   bool png16_ = false;                  // option "png16": 16-bit PNGs decode on the GPU
+  bool gif_ = false;                    // option "gif": a GIF's first frame decodes on the GPU (dg_gif.hip)
   bool jpeg_h1v2_ = false;              // option "jpeg_h1v2": 4:4:0-style JPEGs decode on the GPU
   bool jpeg_cmyk_ = false;              // option "jpeg_cmyk": Adobe CMYK / YCCK JPEGs decode on the GPU (to RGB)
   bool jpeg_multiscan_ = false;         // option "jpeg_multiscan": non-interleaved baseline JPEGs decode on the GPU

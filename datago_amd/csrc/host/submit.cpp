@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "../dg_entropy.h"
+#include "../dg_gif.h"
 #include "../dg_jenc_tree.h"
 #include "../dg_pixel.h"
 #include "../kernels.h"
@@ -103,7 +104,7 @@ static uint32_t h_mfma_steps(const ResizePass &ps) {
 // Row stride of the decoded image a JPEG's or PNG's first pass (or k_copy) reads:
 // the RGB image or the PNG's pixels, or the luma plane of a gray JPEG.
 static uint32_t decoded_stride(const ImageDesc &d) {
-  return (d.fmt == kFmtPng || d.ncomp >= 3) ? d.pix_stride : d.cbw[0] * 8;
+  return (d.fmt != kFmtJpeg || d.ncomp >= 3) ? d.pix_stride : d.cbw[0] * 8;
 }
 
 struct Layout {
@@ -307,6 +308,9 @@ void Context::plan_images(const SubmitArgs &a, Batch &b) {
     } else if (p.fmt == kFmtPng && p.png.status == PH_OK) {
       m.original_width = p.png.width;
       m.original_height = p.png.height;
+    } else if (p.fmt == kFmtGif && p.gif.status == GH_OK) {  // the logical screen
+      m.original_width = p.gif.width;
+      m.original_height = p.gif.height;
     }
     m.width = p.out_w;
     m.height = p.out_h;
@@ -339,6 +343,7 @@ dg_status Context::pool_tables(Batch &b) {
     const ImagePlan &p = b.plans[i];
     // (planning may run on pool threads; dg_last_error is the caller's)
     if (p.status == DG_ERR_UNSUPPORTED && p.fmt == kFmtPng && p.png.depth == 16) set_error(p.png.why);
+    if (p.status && p.fmt == kFmtGif && p.gif.why[0]) set_error(p.gif.why);
     if (p.status || p.fmt != kFmtJpeg) continue;
     hneed += (p.hdr.progressive || p.hdr.multiscan) ? p.hdr.tables.size() : 2u * (size_t)p.hdr.ncomp;
     qneed += (size_t)p.hdr.ncomp;
@@ -436,6 +441,8 @@ void Context::layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl) {
     for (int s_ = 0; s_ < kStages; s_++) o.pass_cache[s_] = -1;
     if (p.fmt == kFmtPng)
       layout_png(a, i, b, bl, d, o);
+    else if (p.fmt == kFmtGif)
+      layout_gif(a, i, b, bl, d, o);
     else
       layout_jpeg(a, i, b, bl, d, o);
     const int last_stage = plan_resize(p, b, bl, d, o);
@@ -583,6 +590,36 @@ void Context::layout_png(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, 
   }
   if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
   b.any_png = true;
+}
+
+// A GIF (option "gif"): the code stream (gathered only when the sub-block chain is not 255, .., 255, last),
+// the frame's index plane and the Rgba8 screen, which then is what an RGBA8 PNG's pixels are.
+void Context::layout_gif(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
+  const GifHeader &g = b.plans[i].gif;
+  d.fmt = kFmtGif;
+  d.width = g.width;
+  d.height = g.height;
+  d.dec_c = 4;
+  GifDesc &gd = d.gif;
+  gd.nbytes = (uint32_t)g.nbytes;
+  gd.blocked = g.closed ? 1u : 0u;
+  gd.mcs = (uint32_t)g.min_code_size;
+  gd.npal = (uint32_t)g.npal;
+  gd.left = g.left;
+  gd.top = g.top;
+  gd.fw = g.fw;
+  gd.fh = g.fh;
+  gd.interlace = (uint32_t)g.interlace;
+  if (!g.closed) o.zs = bl.L.take((size_t)g.nbytes + 64, 256);
+  o.raw = bl.L.take((size_t)g.fw * g.fh + 64, 256);
+  d.pix_stride = (uint32_t)align_up((size_t)g.width * 4, 16);
+  o.pix = bl.late().take((size_t)d.pix_stride * g.height);
+  o.late |= bl.alias ? 2u : 0u;
+  while (b.blob.size() % 4) b.blob.push_back(0);  // k_gif_expand loads whole entries
+  o.pal = b.blob.size();
+  b.blob.insert(b.blob.end(), &g.pal[0][0], &g.pal[0][0] + 1024);
+  if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
+  b.any_gif = true;
 }
 
 void Context::layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
@@ -1169,8 +1206,32 @@ static void patch_png(const PngHeader &g, const uint8_t *src, char *S, const Off
     j.src = (uint64_t)(uintptr_t)(src + g.idat_off[c]);
     j.dst = pd.zs + zo;
     j.len = g.idat_len[c];
-    j.pad = 0;
+    j.count = 0;
     zo += g.idat_len[c];
+    b.gjobs.push_back(j);
+  }
+}
+
+static void patch_gif(const GifHeader &g, const uint8_t *src, char *S, const Offs &o, ImageDesc &d, Batch &b) {
+  GifDesc &gd = d.gif;
+  gd.idx = (uint64_t)(uintptr_t)(S + o.raw);
+  d.pix = (uint64_t)(uintptr_t)(S + o.pix);
+  gd.pal = o.pal + 1;  // blob offset + 1, made absolute with the meta buffer
+  if (g.closed) {      // k_gif_lzw reads through the chain
+    gd.src = (uint64_t)(uintptr_t)(src + g.data_off);
+    gd.src_end = gd.src + (g.nbytes ? gif_src_index((uint32_t)g.nbytes - 1u, 1u) + 1u : 0u);
+    return;
+  }
+  gd.src = (uint64_t)(uintptr_t)(S + o.zs);
+  gd.src_end = gd.src + g.nbytes;
+  uint64_t zo = 0;
+  for (const GifRun &r : g.runs) {
+    GatherJob j;
+    j.src = (uint64_t)(uintptr_t)(src + r.off);
+    j.dst = gd.src + zo;
+    j.len = r.len;
+    j.count = r.count;
+    zo += (uint64_t)r.len * r.count;
     b.gjobs.push_back(j);
   }
 }
@@ -1205,6 +1266,8 @@ void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const Bat
     }
     if (d.fmt == kFmtPng)
       patch_png(b.plans[i].png, src, S, o, d, b);
+    else if (d.fmt == kFmtGif)
+      patch_gif(b.plans[i].gif, src, S, o, d, b);
     else
       patch_jpeg(b.plans[i].hdr, src, sl, o, b.desc_of[i], b);
     patch_passes(S, o, b.desc_of[i], b);
@@ -1288,7 +1351,7 @@ void Context::prog_scan_records(const JpegHeader &h, const uint8_t *src, int di,
 // pix / plane and out are set).
 void Context::patch_passes(char *S, const Offs &o, int di, Batch &b) {
   ImageDesc &d = b.descs[di];
-  uint64_t cur = (d.fmt == kFmtPng || d.ncomp >= 3) ? d.pix : d.plane[0];
+  uint64_t cur = (d.fmt != kFmtJpeg || d.ncomp >= 3) ? d.pix : d.plane[0];
   const uint64_t decoded = cur;
   for (int s = 0; s < kStages; s++) {
     ResizePass &ps = d.pass[s];
@@ -1351,8 +1414,11 @@ void Context::build_lists(Batch &b) {
     cost_sort(b.lists[L_SYNC]);
     cost_sort(b.lists[L_HUFF]);
   }
-  for (uint32_t j = 0; j < (uint32_t)b.gjobs.size(); j++)
-    for (uint32_t pc = 0; pc * kGatherPiece < b.gjobs[j].len; pc++) b.lists[L_GATHER].push_back({j, pc});
+  for (uint32_t j = 0; j < (uint32_t)b.gjobs.size(); j++) {
+    const GatherJob &gj = b.gjobs[j];  // count != 0: a run of a GIF's sub-blocks
+    const uint64_t bytes = gj.count ? (uint64_t)gj.len * gj.count : gj.len;
+    for (uint32_t pc = 0; (uint64_t)pc * kGatherPiece < bytes; pc++) b.lists[gj.count ? L_GIF_GATHER : L_GATHER].push_back({j, pc});
+  }
   if (b.uf_n) {  // unfilter bands in ticket order: the j-th band of every plane, j = 0, 1, ...
     std::vector<std::vector<uint32_t>> per;  // per PNG image: pass << 24 | band, pass-major
     std::vector<uint32_t> who;
@@ -1439,7 +1505,10 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
       const uint32_t cnt = d.aop[k].width * d.aop[k].rows;
       for (uint32_t it = 0; it < cnt; it += 256) b.lists[L_ALPHA0 + k].push_back({I, it});
     }
-  if (d.fmt == kFmtPng) {
+  if (d.fmt == kFmtGif) {
+    b.lists[L_GIF_LZW].push_back({I, 0});
+    for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_GIF_EXPAND].push_back({I, it});
+  } else if (d.fmt == kFmtPng) {
     b.lists[L_PNG].push_back({I, 0});
     if (d.png.nchunks) {
       b.lists[L_INF_RES].push_back({I, 0});
@@ -1560,6 +1629,7 @@ dg_status Context::stage_and_upload(const SubmitArgs &a, Slot &sl, Batch &b, con
   if (st) return st;
   for (ImageDesc &d : b.descs) {
     if (d.fmt == kFmtPng && d.png.pal) d.png.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.png.pal - 1);
+    if (d.fmt == kFmtGif) d.gif.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.gif.pal - 1);
     if (d.enc.active) {
       d.enc.hdr = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.enc.hdr - 1);
       if (!d.enc.png) d.enc.tab = d.enc.tab_std = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + b.enctab_off);

@@ -114,6 +114,11 @@ void launch_png_unfilter(hipStream_t st, ImageDesc *imgs, const WgItem *tasks, u
 void launch_png_expand(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // 16-bit images: 256 pixel pairs per workgroup (byte swap, tRNS key, Adam7 scatter)
 void launch_png_expand16(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// GIF (dg_gif.hip, option "gif"): gather = one kGatherPiece of a run of sub-blocks (GatherJob::count != 0) per
+// workgroup, lzw = one 64-thread workgroup (one wave) per image, expand = 256 screen pixels per workgroup
+void launch_gif_gather(hipStream_t st, const GatherJob *jobs, const WgItem *list, uint32_t nwg);
+void launch_gif_lzw(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_gif_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // 16-bit resize (dg_resize16.hip, option "resize16"): taps = 256 table entries of a pass per workgroup
 // (item0 bit 31 = pass), v = 256 sample quads of an intermediate row, h = 256 output pixels of a row
 void launch_r16_taps(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);

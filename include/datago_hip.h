@@ -63,7 +63,7 @@ typedef enum dg_status {
 } dg_status;
 
 /* Image formats reported by dg_probe. */
-enum { DG_FMT_UNKNOWN = 0, DG_FMT_JPEG = 1, DG_FMT_PNG = 2 };
+enum { DG_FMT_UNKNOWN = 0, DG_FMT_JPEG = 1, DG_FMT_PNG = 2, DG_FMT_GIF = 3 };
 
 /* Mirrors ImageTransformConfig (image_processing.rs:43-70) + ImageEncoding (:24-30). */
 typedef struct dg_image_config {
@@ -111,11 +111,11 @@ dg_status dg_aspect_ratio_to_str(uint32_t w, uint32_t h, char *out, size_t cap);
 typedef struct dg_probe_info {
   int32_t format;         /* DG_FMT_* */
   uint32_t width, height;
-  int32_t components;     /* 1 (L8) or 3 (RGB8) for JPEG */
+  int32_t components;     /* 1 (L8) or 3 (RGB8) for JPEG; 4 (Rgba8 on the logical screen) for GIF */
   int32_t bit_depth;      /* bits per channel (8; 16 for a 16-bit PNG) */
   int32_t h_samp[4], v_samp[4];
   int32_t progressive, arithmetic, precision, restart_interval;
-  int32_t gpu_supported;  /* 1 if dg_submit would decode it on the GPU */
+  int32_t gpu_supported;  /* 1 if dg_submit would decode it on the GPU with the default options (0 for a GIF) */
 } dg_probe_info;
 
 /* Header-only: lets the caller compute the bucket and size the output before
@@ -323,6 +323,20 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 (the reference resizes it with image's own f32 Lanczos3: option "resize16"), and one
  *                 that would reach an encoder as 16-bit (pre_encode_images without image_to_rgb8;
  *                 option "penc16" takes it into the PNG encoder)
+ *   "gif"         1 = decode GIF87a / GIF89a files on the GPU (default 0: DG_ERR_CORRUPT from every entry
+ *                 point, like any format the library does not know; dg_probe names a GIF either way, with
+ *                 gpu_supported 0).  The output is what image 0.25's GifDecoder returns for
+ *                 load_from_memory: the first frame composited on the logical screen as Rgba8 (palette RGB
+ *                 with alpha 255, alpha 0 and the RGB kept at the last Graphic Control Extension's
+ *                 transparent index, (0,0,0,0) outside the frame's rectangle, a frame past the screen
+ *                 clipped); later frames are ignored.  From there the image behaves as an RGBA8 PNG of
+ *                 the same pixels (meta 4 / 8 before the transform, original_* = the logical screen).
+ *                 DG_ERR_UNSUPPORTED, each with a dg_last_error text of its own: an LZW code above the
+ *                 next free code, image data ending before the frame is complete, a pixel index past the
+ *                 colour table, a minimum code size outside 2..8, a zero screen or frame dimension, a
+ *                 screen over 512 MiB of Rgba8 or over the GPU path's 32-bit working set.  DG_ERR_CORRUPT:
+ *                 a file ending inside a header, table, extension or sub-block chain, no image
+ *                 descriptor, no colour table.  Any other value: DG_ERR_INVALID
  *   "resize16"    1 = with "png16", a 16-bit PNG whose size differs from its bucket's (the closest or a
  *                 forced one) is resized to it on the GPU (default 0: DG_ERR_UNSUPPORTED).  The
  *                 resize is the image crate's resize_to_fill(w, h, Lanczos3), as the reference
