@@ -30,7 +30,7 @@ DG_OK, DG_ERR_UNSUPPORTED, DG_ERR_CORRUPT, DG_ERR_OOM, DG_ERR_BAD_BUCKET = 0, 1,
 DG_ERR_INVALID, DG_ERR_SMALL_BUFFER, DG_ERR_DEVICE, DG_ERR_NOT_READY = 5, 6, 7, 8
 STATUS_NAMES = {0: "OK", 1: "UNSUPPORTED", 2: "CORRUPT", 3: "OOM", 4: "BAD_BUCKET", 5: "INVALID",
                 6: "SMALL_BUFFER", 7: "DEVICE", 8: "NOT_READY"}
-DG_FMT_UNKNOWN, DG_FMT_JPEG, DG_FMT_PNG, DG_FMT_GIF = 0, 1, 2, 3
+DG_FMT_UNKNOWN, DG_FMT_JPEG, DG_FMT_PNG, DG_FMT_GIF, DG_FMT_WEBP = 0, 1, 2, 3, 4
 
 # exported symbols (must match include/datago_hip.h; checked by tests)
 EXPORTS = [
@@ -330,7 +330,7 @@ class Context:
                  image_to_rgb8: bool = False, pre_encode_images: bool = False, encode_format: int = 0,
                  jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False,
                  resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False,
-                 jenc_optimize: bool = False, gif: bool = False):
+                 jenc_optimize: bool = False, gif: bool = False, webp: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -357,6 +357,8 @@ class Context:
             self.set_option("jenc_optimize", 1)
         if gif:  # GIF files: the first frame on the logical screen as RGBA8; off: DG_ERR_CORRUPT like any unknown format
             self.set_option("gif", 1)
+        if webp:  # lossless WebP files: Rgb8 / Rgba8 as the file says; off: DG_ERR_CORRUPT like any unknown format
+            self.set_option("webp", 1)
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

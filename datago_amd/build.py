@@ -29,10 +29,12 @@ SOURCES = [
     ("dg_band.hip", True),
     ("dg_resize16.hip", True),
     ("dg_gif.hip", True),
+    ("dg_vp8l.hip", True),
     ("host/jpeg_enc.cpp", False),
     ("host/wds.cpp", False),
     ("host/png_header.cpp", False),
     ("host/gif_header.cpp", False),
+    ("host/webp_header.cpp", False),
     ("host/pipeline.cpp", False),
     ("host/submit.cpp", False),
     ("host/capi.cpp", False),

@@ -176,7 +176,7 @@ constexpr uint32_t kHBandsDefault = 16;  // default ResizePass::bands (8 -> 16: 
 constexpr int kStages = 4;  // R1.H, R1.V, R2.H, R2.V
 
 // ---- PNG (ImageDesc::fmt == kFmtPng)
-constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1, kFmtGif = 2;
+constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1, kFmtGif = 2, kFmtWebp = 3;
 // IDAT payloads are gathered into one contiguous zlib stream (k_png_gather),
 // inflated into filtered scanlines (k_png_inflate, one wave per image),
 // unfiltered (k_png_unfilter, one wave per 64-row band on a diagonal
@@ -226,6 +226,33 @@ struct GifDesc {
 constexpr uint32_t kGifFailCode = 1;     // a code above the next free one, or the next free one straight after a clear
 constexpr uint32_t kGifFailShort = 2;    // the data ends (or an end code comes) before fw x fh indices
 constexpr uint32_t kGifFailPalette = 3;  // an index at or past the colour table's size
+
+// ---- lossless WebP (ImageDesc::fmt == kFmtWebp, option "webp"): a VP8L chunk as Rgb8 / Rgba8.
+// k_vp8l_decode (one wave per image, dg_vp8l.h) reads the bitstream after the 5-byte header in place:
+// the transform list, their sub-images and the entropy-decoded ARGB plane go to the work arena
+// (vp8l_*_off), the prefix-code tables to the table area.  k_vp8l_inverse applies the inverse
+// transforms in reverse order of reading, k_vp8l_store writes pix (dec_c 3 drops the alpha).
+// A broken stream sets ImageDesc::status and Vp8lDesc::fail (kVp8lFail*) names it.
+struct Vp8lDesc {
+  uint64_t src;          // the bitstream after the VP8L header, in the file
+  uint64_t src_end;      // one past its last byte (loads stay below it)
+  uint64_t work;         // work arena: vp8l_work_words(width, height) u32
+  uint64_t tabs;         // table area: groups_cap x kVp8lGroupWords u32
+  uint32_t nbytes;       // bitstream bytes
+  uint32_t groups_cap;   // prefix-code groups the table area holds
+  uint32_t fail;         // kVp8lFail*: written by k_vp8l_decode
+  uint32_t ntrans;       // written by k_vp8l_decode: transforms read,
+  uint32_t trans[4];     // ... each as vp8l_trans_pack, in the order read,
+  uint32_t xsize;        // ... the width of the decoded (packed) image in plane 0,
+  uint32_t npal;         // ... and the colour table's entries
+  uint32_t final_plane;  // written by k_vp8l_inverse: the plane that holds the ARGB image
+};
+constexpr uint32_t kVp8lFailBits = 1;       // the data ends before the image is complete
+constexpr uint32_t kVp8lFailCode = 2;       // a prefix code neither complete nor single-symbol (or its description broken)
+constexpr uint32_t kVp8lFailCopy = 3;       // a copy reaching before the first pixel or past the last
+constexpr uint32_t kVp8lFailCache = 4;      // a cache index with no cache, or cache bits outside 1..11
+constexpr uint32_t kVp8lFailTransform = 5;  // a transform used twice
+constexpr uint32_t kVp8lFailGroups = 6;     // more groups than the table area holds (DG_ERR_UNSUPPORTED)
 
 // Adam7 pass p of a W x H image (PNG spec 8.2): origin (x0, y0), spacing (dx, dy)
 DG_HD uint32_t png_a7(uint32_t p, uint32_t k) {
@@ -460,7 +487,7 @@ struct ImageDesc {
   uint32_t final_src_c;
   uint32_t color_fused;     // 1: pass[0] converts colour itself, pix is never written
   // ---- format, PNG, alpha handling, final conversion
-  uint32_t fmt;             // kFmtJpeg / kFmtPng / kFmtGif
+  uint32_t fmt;             // kFmtJpeg / kFmtPng / kFmtGif / kFmtWebp
   uint32_t prog;            // progressive JPEG: scans decoded by k_prog_scan (0: sequential)
   uint32_t crec;            // bit c: component c's plane holds chroma records (dg_plane.h; option "chroma_rec")
   uint32_t copy_mode;       // k_copy: 0 same channels, 1 L->RGB, 2 RGBA->RGB blend over gray,
@@ -472,6 +499,7 @@ struct ImageDesc {
   union {
     PngDesc png;            // fmt == kFmtPng
     GifDesc gif;            // fmt == kFmtGif
+    Vp8lDesc vp8l;          // fmt == kFmtWebp
   };
   AlphaOp aop[kAlphaPoints];
   EncDesc enc;

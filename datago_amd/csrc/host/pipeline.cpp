@@ -407,6 +407,22 @@ dg_status Context::set_option(const std::string &k, int64_t v) {
     gif_ = v != 0;
     return DG_OK;
   }
+  if (k == "webp") {
+    // Still lossless WebP files (a VP8L image chunk, simple or behind VP8X) on the
+    // GPU (default off: DG_ERR_CORRUPT like any format the library does not
+    // know).  1: plan_image takes the file, k_vp8l_decode reads the bitstream,
+    // k_vp8l_inverse undoes the transforms and k_vp8l_store writes Rgba8 when
+    // the file says it has alpha (the VP8L header's bit, or the VP8X flag of an
+    // extended file) and Rgb8 otherwise (dg_vp8l.hip): what image 0.25's
+    // WebPDecoder returns for load_from_memory.  From there it is an 8-bit RGB /
+    // RGBA PNG's pixels.  Animated and extended lossy files come back
+    // DG_ERR_UNSUPPORTED, a simple lossy file stays an unknown format.
+    // dg_probe names a lossless or extended WebP either way and keeps
+    // describing the default options.
+    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
+    webp_ = v != 0;
+    return DG_OK;
+  }
   if (k == "jpeg_h1v2") {
     // Colour JPEGs with a component at the full horizontal and half the
     // vertical rate (4:4:0, what a lossless 90-degree rotation makes of 4:2:2;
@@ -1468,6 +1484,22 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     W = p.gif.width;
     H = p.gif.height;
     C = 4;
+  } else if (webp_ && is_webp(h, len)) {  // option "webp"
+    p.fmt = kFmtWebp;
+    parse_webp_header(h, len, p.webp);
+    if (p.webp.status != WH_OK) {
+      p.status = p.webp.status == WH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
+      return DG_OK;
+    }
+    // the limits of the GIF path: the pixel buffer and the bit count stay 32-bit addressable
+    if ((uint64_t)p.webp.width * p.webp.height * 4ull >= (1ull << 31) || p.webp.nbytes >= (1ull << 28)) {
+      p.webp.why = "WebP: image too large for the GPU path";
+      p.status = DG_ERR_UNSUPPORTED;
+      return DG_OK;
+    }
+    W = p.webp.width;
+    H = p.webp.height;
+    C = p.webp.alpha ? 4 : 3;
   } else {
     if (!is_jpeg(h, len)) {
       p.status = DG_ERR_CORRUPT;
@@ -1571,7 +1603,10 @@ dg_status Context::output_size(const uint8_t *bytes, size_t len, int32_t forced,
   plan_image(bytes, len, forced, p);
   *nbytes = p.out_bytes;
   if (p.status)
-    set_error(p.fmt == kFmtPng ? p.png.why : p.fmt == kFmtGif ? p.gif.why : (p.hdr.why ? p.hdr.why : "unsupported"));
+    set_error(p.fmt == kFmtPng    ? p.png.why
+              : p.fmt == kFmtGif  ? p.gif.why
+              : p.fmt == kFmtWebp ? p.webp.why
+                                  : (p.hdr.why ? p.hdr.why : "unsupported"));
   return (dg_status)p.status;
 }
 
@@ -1814,8 +1849,13 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     launch_gif_gather(sl.st, (const GatherJob *)(M + b.gjob_off), lst(L_GIF_GATHER), cnt(L_GIF_GATHER));
     launch_gif_lzw(sl.st, dm, lst(L_GIF_LZW), cnt(L_GIF_LZW));
   }
+  if (!from_fix && b.any_webp) {  // lossless WebP: bitstream -> ARGB plane -> inverse transforms
+    launch_vp8l_decode(sl.st, dm, lst(L_VP8L), cnt(L_VP8L));
+    launch_vp8l_inverse(sl.st, dm, lst(L_VP8L), cnt(L_VP8L));
+  }
   if (next()) return DG_ERR_DEVICE;
   if (!from_fix && b.any_gif) launch_gif_expand(sl.st, dm, lst(L_GIF_EXPAND), cnt(L_GIF_EXPAND));
+  if (!from_fix && b.any_webp) launch_vp8l_store(sl.st, dm, lst(L_VP8L_STORE), cnt(L_VP8L_STORE));
   if (!from_fix && b.any_png) {
     if (b.uf_n) {
       uint32_t *uf = (uint32_t *)((char *)sl.scratch.p + b.uf_flags_off);
@@ -2181,6 +2221,16 @@ dg_status Context::finish_body(Slot &sl) {
                 : f == kGifFailShort ? "GIF: image data ends before the frame is complete"
                 : f == kGifFailPalette ? "GIF: pixel index past the colour table"
                                        : "GIF: decode failed");
+    }
+    if (status && back[b.desc_of[i]].fmt == kFmtWebp) {  // what k_vp8l_decode met in the stream
+      const uint32_t f = back[b.desc_of[i]].vp8l.fail;
+      set_error(f == kVp8lFailBits        ? "WebP: image data ends before the image is complete"
+                : f == kVp8lFailCode      ? "WebP: prefix code neither complete nor single-symbol"
+                : f == kVp8lFailCopy      ? "WebP: copy reaches before the first or past the last pixel"
+                : f == kVp8lFailCache     ? "WebP: colour-cache index or size outside the format"
+                : f == kVp8lFailTransform ? "WebP: transform used twice"
+                : f == kVp8lFailGroups    ? "WebP: more prefix-code groups than the GPU path holds"
+                                          : "WebP: decode failed");
     }
     if (status) b.mptr[i]->status = status;
     if (b.plans[i].encode) {

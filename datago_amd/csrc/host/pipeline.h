@@ -16,6 +16,7 @@
 #include "buckets.h"
 #include "jpeg_header.h"
 #include "gif_header.h"
+#include "webp_header.h"
 #include "png_header.h"
 #include "jpeg_enc.h"
 #include "host_pool.h"
@@ -39,6 +40,7 @@ struct ImagePlan {
   JpegHeader hdr;
   PngHeader png;
   GifHeader gif;  // fmt == kFmtGif (option "gif")
+  WebpHeader webp;  // fmt == kFmtWebp (option "webp")
   int bucket = -1;
   uint32_t out_w = 0, out_h = 0, out_c = 0;
   uint64_t out_bytes = 0;
@@ -73,8 +75,8 @@ struct Batch {
   std::vector<ImageDesc> descs;
   std::vector<int> desc_of;           // image -> desc index or -1
   // workgroup lists (host copies) and their offsets in the device meta buffer
-  std::vector<WgItem> lists[48];
-  size_t list_off[48] = {0};
+  std::vector<WgItem> lists[52];
+  size_t list_off[52] = {0};
   // PNG: IDAT gather jobs and palettes, uploaded with the descriptors
   std::vector<GatherJob> gjobs;
   size_t gjob_off = 0;
@@ -93,6 +95,7 @@ struct Batch {
   size_t blob_off = 0;
   bool any_png = false, any_alpha = false, any_enc = false;
   bool any_gif = false;   // a GIF (option "gif"): k_gif_gather, k_gif_lzw, k_gif_expand
+  bool any_webp = false;  // a lossless WebP (option "webp"): k_vp8l_decode, k_vp8l_inverse, k_vp8l_store
   bool penc_dyn = false;  // a PNG re-encode with option "penc_dynamic": histogram, k_penc_tree, dynamic count / write
   bool jenc_opt = false;  // a JPEG re-encode with option "jenc_optimize": k_enc_hist, k_enc_tree, per-image tables
   bool any_fused = false;  // some image's IDCT runs inside k_huff_write
@@ -208,9 +211,10 @@ enum ListId {
   L_CMYK,                                                   // four planes -> RGB of a CMYK / YCCK JPEG (k_cmyk)
   L_MS_ZERO,                                                // multiscan parents: blocks no scan codes (k_ms_zero)
   L_GIF_GATHER, L_GIF_LZW, L_GIF_EXPAND,                    // GIF decode (dg_gif.hip)
+  L_VP8L, L_VP8L_STORE,                                     // lossless WebP decode (dg_vp8l.hip): per image, per 256 pixels
   L_COUNT
 };
-static_assert((int)L_COUNT <= 48, "Batch::lists");
+static_assert((int)L_COUNT <= 52, "Batch::lists");
 
 // A recently pooled table (pool_huff / pool_quant): its key bytes and slot.
 struct RecentTab {
@@ -275,6 +279,7 @@ class Context {
   void layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl);  // per image: the next five
   void layout_png(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_gif(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  void layout_webp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_entropy_stream(size_t scan_len, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
@@ -548,6 +553,7 @@ class Context {
   bool progressive_ = true;             // option "progressive"
   bool png16_ = false;                  // option "png16": 16-bit PNGs decode on the GPU
   bool gif_ = false;                    // option "gif": a GIF's first frame decodes on the GPU (dg_gif.hip)
+  bool webp_ = false;                   // option "webp": a lossless WebP decodes on the GPU (dg_vp8l.hip)
   bool jpeg_h1v2_ = false;              // option "jpeg_h1v2": 4:4:0-style JPEGs decode on the GPU
   bool jpeg_cmyk_ = false;              // option "jpeg_cmyk": Adobe CMYK / YCCK JPEGs decode on the GPU (to RGB)
   bool jpeg_multiscan_ = false;         // option "jpeg_multiscan": non-interleaved baseline JPEGs decode on the GPU

@@ -15,6 +15,7 @@
 
 #include "../dg_entropy.h"
 #include "../dg_gif.h"
+#include "../dg_vp8l.h"
 #include "../dg_jenc_tree.h"
 #include "../dg_pixel.h"
 #include "../kernels.h"
@@ -311,6 +312,9 @@ void Context::plan_images(const SubmitArgs &a, Batch &b) {
     } else if (p.fmt == kFmtGif && p.gif.status == GH_OK) {  // the logical screen
       m.original_width = p.gif.width;
       m.original_height = p.gif.height;
+    } else if (p.fmt == kFmtWebp && p.webp.status == WH_OK) {
+      m.original_width = p.webp.width;
+      m.original_height = p.webp.height;
     }
     m.width = p.out_w;
     m.height = p.out_h;
@@ -344,6 +348,7 @@ dg_status Context::pool_tables(Batch &b) {
     // (planning may run on pool threads; dg_last_error is the caller's)
     if (p.status == DG_ERR_UNSUPPORTED && p.fmt == kFmtPng && p.png.depth == 16) set_error(p.png.why);
     if (p.status && p.fmt == kFmtGif && p.gif.why[0]) set_error(p.gif.why);
+    if (p.status && p.fmt == kFmtWebp && p.webp.why[0]) set_error(p.webp.why);
     if (p.status || p.fmt != kFmtJpeg) continue;
     hneed += (p.hdr.progressive || p.hdr.multiscan) ? p.hdr.tables.size() : 2u * (size_t)p.hdr.ncomp;
     qneed += (size_t)p.hdr.ncomp;
@@ -443,6 +448,8 @@ void Context::layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl) {
       layout_png(a, i, b, bl, d, o);
     else if (p.fmt == kFmtGif)
       layout_gif(a, i, b, bl, d, o);
+    else if (p.fmt == kFmtWebp)
+      layout_webp(a, i, b, bl, d, o);
     else
       layout_jpeg(a, i, b, bl, d, o);
     const int last_stage = plan_resize(p, b, bl, d, o);
@@ -620,6 +627,27 @@ void Context::layout_gif(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, 
   b.blob.insert(b.blob.end(), &g.pal[0][0], &g.pal[0][0] + 1024);
   if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
   b.any_gif = true;
+}
+
+// A lossless WebP (option "webp"), sized from the header alone: the coded bytes are read in place; the work
+// arena (two ARGB planes, three sub-image planes of at most ceil(w/4) x ceil(h/4), the colour table), the
+// prefix-code table area and the Rgb8 / Rgba8 pixels, which then are what an 8-bit PNG's pixels are.
+void Context::layout_webp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
+  const WebpHeader &g = b.plans[i].webp;
+  d.fmt = kFmtWebp;
+  d.width = g.width;
+  d.height = g.height;
+  d.dec_c = g.alpha ? 4 : 3;
+  Vp8lDesc &vd = d.vp8l;
+  vd.nbytes = (uint32_t)g.nbytes;
+  vd.groups_cap = vp8l_groups_cap(g.width, g.height);
+  o.raw = bl.L.take((size_t)vp8l_work_words(g.width, g.height) * 4, 256);
+  o.zs = bl.L.take((size_t)vd.groups_cap * kVp8lGroupWords * 4, 256);
+  d.pix_stride = (uint32_t)align_up((size_t)g.width * d.dec_c, 16);
+  o.pix = bl.late().take((size_t)d.pix_stride * g.height);
+  o.late |= bl.alias ? 2u : 0u;
+  if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
+  b.any_webp = true;
 }
 
 void Context::layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
@@ -1236,6 +1264,15 @@ static void patch_gif(const GifHeader &g, const uint8_t *src, char *S, const Off
   }
 }
 
+static void patch_webp(const WebpHeader &g, const uint8_t *src, char *S, const Offs &o, ImageDesc &d) {
+  Vp8lDesc &vd = d.vp8l;
+  vd.work = (uint64_t)(uintptr_t)(S + o.raw);
+  vd.tabs = (uint64_t)(uintptr_t)(S + o.zs);
+  d.pix = (uint64_t)(uintptr_t)(S + o.pix);
+  vd.src = (uint64_t)(uintptr_t)(src + g.data_off);
+  vd.src_end = vd.src + g.nbytes;
+}
+
 // ---- 4. patch device addresses
 void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const BatchLayout &bl) {
   char *S = (char *)sl.scratch.p;
@@ -1268,6 +1305,8 @@ void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const Bat
       patch_png(b.plans[i].png, src, S, o, d, b);
     else if (d.fmt == kFmtGif)
       patch_gif(b.plans[i].gif, src, S, o, d, b);
+    else if (d.fmt == kFmtWebp)
+      patch_webp(b.plans[i].webp, src, S, o, d);
     else
       patch_jpeg(b.plans[i].hdr, src, sl, o, b.desc_of[i], b);
     patch_passes(S, o, b.desc_of[i], b);
@@ -1505,7 +1544,10 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
       const uint32_t cnt = d.aop[k].width * d.aop[k].rows;
       for (uint32_t it = 0; it < cnt; it += 256) b.lists[L_ALPHA0 + k].push_back({I, it});
     }
-  if (d.fmt == kFmtGif) {
+  if (d.fmt == kFmtWebp) {
+    b.lists[L_VP8L].push_back({I, 0});
+    for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_VP8L_STORE].push_back({I, it});
+  } else if (d.fmt == kFmtGif) {
     b.lists[L_GIF_LZW].push_back({I, 0});
     for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_GIF_EXPAND].push_back({I, it});
   } else if (d.fmt == kFmtPng) {

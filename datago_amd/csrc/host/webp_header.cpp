@@ -1,0 +1,84 @@
+// webp_header.cpp — WebP container walk (see webp_header.h).
+//
+// What is structurally broken (a chunk past the RIFF size or the file, a bad
+// VP8L signature or version, no image chunk, a VP8X canvas that differs from
+// the VP8L size) is WH_CORRUPT; what is well-formed but outside the GPU path
+// (animation, a lossy image chunk) is WH_UNSUPPORTED, so the caller's CPU
+// decoder decides.  A structural break met first wins.
+#include "webp_header.h"
+
+#include <string.h>
+
+namespace dg {
+
+bool is_webp(const uint8_t *d, size_t n) {
+  return n >= 16 && !memcmp(d, "RIFF", 4) && !memcmp(d + 8, "WEBP", 4) && (!memcmp(d + 12, "VP8L", 4) || !memcmp(d + 12, "VP8X", 4));
+}
+
+static void fail(WebpHeader &h, int st, const char *why) {
+  h.status = st;
+  h.why = why;
+}
+
+static uint32_t le(const uint8_t *p, int n) {
+  uint32_t v = 0;
+  for (int i = 0; i < n; i++) v |= (uint32_t)p[i] << (8 * i);
+  return v;
+}
+
+void parse_webp_header(const uint8_t *d, size_t n, WebpHeader &h) {
+  h = WebpHeader();
+  if (!is_webp(d, n)) return fail(h, WH_CORRUPT, "not a WebP");
+  const uint64_t riff = le(d + 4, 4);
+  if (riff < 4 || 8 + riff > n) return fail(h, WH_CORRUPT, "WebP: truncated chunk");
+  const uint64_t end = 8 + riff;
+  uint64_t pos = 12;
+  bool first = true;
+  const char *unsup = nullptr;  // the first well-formed thing outside the GPU path
+  for (;;) {
+    if (pos + 8 > end) {
+      if (unsup) return fail(h, WH_UNSUPPORTED, unsup);
+      return fail(h, WH_CORRUPT, pos >= end ? "WebP: no image chunk" : "WebP: truncated chunk");
+    }
+    const uint8_t *cc = d + pos;
+    const uint64_t len = le(d + pos + 4, 4), body = pos + 8;
+    if (body + len > end) return fail(h, WH_CORRUPT, "WebP: truncated chunk");
+    if (first && !memcmp(cc, "VP8X", 4)) {
+      if (len < 10) return fail(h, WH_CORRUPT, "WebP: truncated chunk");
+      const uint8_t flags = d[body];
+      h.extended = 1;
+      h.alpha = (flags & 0x10) ? 1 : 0;
+      h.canvas_w = 1 + le(d + body + 4, 3);
+      h.canvas_h = 1 + le(d + body + 7, 3);
+      h.width = h.canvas_w;  // what dg_probe reports for a file that never reaches a VP8L header
+      h.height = h.canvas_h;
+      if (flags & 0x02) unsup = "WebP: animated WebP";
+    } else if (!memcmp(cc, "ANIM", 4) || !memcmp(cc, "ANMF", 4)) {
+      if (!unsup) unsup = "WebP: animated WebP";
+    } else if (!memcmp(cc, "VP8 ", 4) || !memcmp(cc, "ALPH", 4)) {
+      if (!unsup) unsup = "WebP: lossy WebP";
+    } else if (!memcmp(cc, "VP8L", 4)) {
+      if (unsup) return fail(h, WH_UNSUPPORTED, unsup);
+      if (len < 5) return fail(h, WH_CORRUPT, "WebP: truncated chunk");
+      if (d[body] != 0x2f) return fail(h, WH_CORRUPT, "WebP: bad VP8L signature");
+      const uint32_t v = le(d + body + 1, 4);
+      h.width = 1 + (v & 0x3fff);
+      h.height = 1 + ((v >> 14) & 0x3fff);
+      if ((v >> 29) & 7) return fail(h, WH_CORRUPT, "WebP: bad VP8L version");
+      if (h.extended) {
+        if (h.canvas_w != h.width || h.canvas_h != h.height)
+          return fail(h, WH_CORRUPT, "WebP: VP8X canvas size differs from the VP8L size");
+      } else {
+        h.alpha = (int)((v >> 28) & 1);
+      }
+      h.data_off = (uint32_t)(body + 5);
+      h.nbytes = len - 5;
+      h.status = WH_OK;
+      return;
+    }
+    first = false;
+    pos = body + len + (len & 1);
+  }
+}
+
+}  // namespace dg

@@ -1,0 +1,37 @@
+// webp_header.h — host-side WebP container walker (RIFF .. the VP8L chunk's
+// 5-byte header), no pixel work.
+//
+// Replaces the header half of `image::load_from_memory` for a still lossless
+// WebP (image 0.25's WebPDecoder): the RIFF size, the chunks with their even
+// padding, VP8X's canvas size and flags, and the first VP8L chunk's signature,
+// size, alpha bit and version.  Nothing past that header is parsed here:
+// transform data and prefix codes are interleaved with entropy-coded
+// sub-images, so the rest of the stream is k_vp8l_decode's (dg_vp8l.hip).
+//
+// A simple lossy file (RIFF....WEBPVP8 ) is not named by is_webp: it stays an
+// unknown format (DG_ERR_CORRUPT) from every entry point, so the glue's sniff
+// keeps lossy files on its CPU path.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace dg {
+
+enum WebpStatus { WH_OK = 0, WH_UNSUPPORTED = 1, WH_CORRUPT = 2 };
+
+struct WebpHeader {
+  int status = WH_CORRUPT;
+  const char *why = "";
+  int extended = 0;                      // the file starts with VP8X
+  int alpha = 0;                         // Rgba8: VP8X's alpha flag, or the VP8L header's bit in a simple file
+  uint32_t canvas_w = 0, canvas_h = 0;   // VP8X
+  uint32_t width = 0, height = 0;        // the VP8L header (the VP8X canvas until one is read: animated, lossy)
+  uint32_t data_off = 0;                 // file offset of the bitstream after the 5-byte header
+  uint64_t nbytes = 0;                   // its bytes
+};
+
+// RIFF....WEBP followed by VP8L or VP8X.
+bool is_webp(const uint8_t *d, size_t n);
+void parse_webp_header(const uint8_t *d, size_t n, WebpHeader &h);
+
+}  // namespace dg

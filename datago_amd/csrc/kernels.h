@@ -119,6 +119,11 @@ void launch_png_expand16(hipStream_t st, const ImageDesc *imgs, const WgItem *li
 void launch_gif_gather(hipStream_t st, const GatherJob *jobs, const WgItem *list, uint32_t nwg);
 void launch_gif_lzw(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_gif_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// lossless WebP (dg_vp8l.hip, option "webp"): decode and inverse = one 64-thread workgroup (one wave) per
+// image, store = 256 pixels per workgroup
+void launch_vp8l_decode(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_vp8l_inverse(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_vp8l_store(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // 16-bit resize (dg_resize16.hip, option "resize16"): taps = 256 table entries of a pass per workgroup
 // (item0 bit 31 = pass), v = 256 sample quads of an intermediate row, h = 256 output pixels of a row
 void launch_r16_taps(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);

@@ -88,8 +88,10 @@ class ARAwareTransform:
     """Bucket table + the device context that applies it."""
 
     def __init__(self, cfg: ImageTransformConfig, device: int = 0, png16: bool = False, resize16: bool = False,
-                 penc_dynamic: bool = False, penc16: bool = False, jenc_optimize: bool = False, gif: bool = False):
+                 penc_dynamic: bool = False, penc16: bool = False, jenc_optimize: bool = False, gif: bool = False,
+                 webp: bool = False):
         self.cfg = cfg
+        self.webp = webp  # context option "webp": a lossless WebP decodes on the GPU as RGB8 / RGBA8
         self.gif = gif  # context option "gif": a GIF's first frame decodes on the GPU as RGBA8
         self.jenc_optimize = jenc_optimize  # context option "jenc_optimize": JPEG re-encode with per-image Huffman tables
         self.penc_dynamic = penc_dynamic  # context option "penc_dynamic": PNG re-encode with per-image Huffman codes
@@ -121,7 +123,7 @@ class ARAwareTransform:
                                           encode_format=int(enc.encode_format), jpeg_quality=enc.jpeg_quality,
                                           png16=self.png16, resize16=self.resize16, penc16=self.penc16,
                                           penc_dynamic=self.penc_dynamic, jenc_optimize=self.jenc_optimize,
-                                          gif=self.gif)
+                                          gif=self.gif, webp=self.webp)
         return self._ctx[key]
 
 

@@ -63,7 +63,7 @@ typedef enum dg_status {
 } dg_status;
 
 /* Image formats reported by dg_probe. */
-enum { DG_FMT_UNKNOWN = 0, DG_FMT_JPEG = 1, DG_FMT_PNG = 2, DG_FMT_GIF = 3 };
+enum { DG_FMT_UNKNOWN = 0, DG_FMT_JPEG = 1, DG_FMT_PNG = 2, DG_FMT_GIF = 3, DG_FMT_WEBP = 4 };
 
 /* Mirrors ImageTransformConfig (image_processing.rs:43-70) + ImageEncoding (:24-30). */
 typedef struct dg_image_config {
@@ -111,11 +111,12 @@ dg_status dg_aspect_ratio_to_str(uint32_t w, uint32_t h, char *out, size_t cap);
 typedef struct dg_probe_info {
   int32_t format;         /* DG_FMT_* */
   uint32_t width, height;
-  int32_t components;     /* 1 (L8) or 3 (RGB8) for JPEG; 4 (Rgba8 on the logical screen) for GIF */
+  int32_t components;     /* 1 (L8) or 3 (RGB8) for JPEG; 4 (Rgba8 on the logical screen) for GIF;
+                             3 (Rgb8) or 4 (Rgba8) for a lossless or extended WebP */
   int32_t bit_depth;      /* bits per channel (8; 16 for a 16-bit PNG) */
   int32_t h_samp[4], v_samp[4];
   int32_t progressive, arithmetic, precision, restart_interval;
-  int32_t gpu_supported;  /* 1 if dg_submit would decode it on the GPU with the default options (0 for a GIF) */
+  int32_t gpu_supported;  /* 1 if dg_submit would decode it on the GPU with the default options (0 for a GIF or a WebP) */
 } dg_probe_info;
 
 /* Header-only: lets the caller compute the bucket and size the output before
@@ -337,6 +338,25 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 screen over 512 MiB of Rgba8 or over the GPU path's 32-bit working set.  DG_ERR_CORRUPT:
  *                 a file ending inside a header, table, extension or sub-block chain, no image
  *                 descriptor, no colour table.  Any other value: DG_ERR_INVALID
+ *   "webp"        1 = decode still lossless WebP files on the GPU: a RIFF/WEBP file whose image data is a
+ *                 VP8L chunk, alone (simple file) or behind VP8X with ICCP / EXIF / XMP / unknown chunks
+ *                 skipped (default 0: DG_ERR_CORRUPT from every entry point, like any format the library
+ *                 does not know; dg_probe names such a file either way, DG_FMT_WEBP with gpu_supported 0).
+ *                 The output is what image 0.25's WebPDecoder returns for load_from_memory: Rgba8 when
+ *                 the file says it has alpha (the alpha bit of the VP8L header in a simple file, the VP8X
+ *                 alpha flag in an extended one), else Rgb8 with the decoded alpha dropped.  From there
+ *                 the image behaves as an 8-bit RGB / RGBA PNG of the same pixels (meta 3 or 4 / 8).
+ *                 DG_ERR_UNSUPPORTED with a dg_last_error text: "animated WebP" (ANIM / ANMF chunks or
+ *                 the VP8X animation flag), "lossy WebP" (an extended file whose image chunk is VP8,
+ *                 with or without ALPH), more prefix-code groups than the GPU path holds (128; libwebp's
+ *                 encoder was measured at 49 at most), an image too large for the GPU path.
+ *                 DG_ERR_CORRUPT: a truncated chunk, a bad VP8L signature or version, no image chunk, a
+ *                 VP8X canvas size differing from the VP8L size, image data ending early, a prefix code
+ *                 neither complete nor single-symbol, a copy reaching before the first or past the last
+ *                 pixel, colour-cache bits outside 1..11, a transform used twice.  A simple lossy file
+ *                 (RIFF....WEBPVP8 ) is not named by the sniff: it stays DG_ERR_CORRUPT "unknown image
+ *                 format" from dg_probe and DG_ERR_CORRUPT from the submit paths with the option on
+ *                 too, so the glue keeps lossy files on its CPU path.  Any other value: DG_ERR_INVALID
  *   "resize16"    1 = with "png16", a 16-bit PNG whose size differs from its bucket's (the closest or a
  *                 forced one) is resized to it on the GPU (default 0: DG_ERR_UNSUPPORTED).  The
  *                 resize is the image crate's resize_to_fill(w, h, Lanczos3), as the reference
