@@ -345,20 +345,19 @@ class Context:
         self.cfg = cfg
         bt = L.dg_ctx_buckets(h)
         self.buckets = BucketTable(0, 0, 0, 0, _borrowed=bt) if bt else None
-        if png16:  # 16-bit PNGs decode on the GPU (uint16 arrays / tensors); off: DG_ERR_UNSUPPORTED
-            self.set_option("png16", 1)
-        if resize16:  # ... and those that are not their bucket's size resize to it (with png16)
-            self.set_option("resize16", 1)
-        if penc16:  # ... and re-encode as bit-depth-16 PNGs under pre_encode_images with encode_format png
-            self.set_option("penc16", 1)
-        if penc_dynamic:  # PNG re-encode: per-image Huffman codes where they make the file shorter
-            self.set_option("penc_dynamic", 1)
-        if jenc_optimize:  # JPEG re-encode: per-image Huffman tables (libjpeg's optimize_coding rule)
-            self.set_option("jenc_optimize", 1)
-        if gif:  # GIF files: the first frame on the logical screen as RGBA8; off: DG_ERR_CORRUPT like any unknown format
-            self.set_option("gif", 1)
-        if webp:  # lossless WebP files: Rgb8 / Rgba8 as the file says; off: DG_ERR_CORRUPT like any unknown format
-            self.set_option("webp", 1)
+        for key, on in (
+                ("png16", png16),  # 16-bit PNGs decode on the GPU (uint16 arrays / tensors); off: DG_ERR_UNSUPPORTED
+                ("resize16", resize16),  # ... and those that are not their bucket's size resize to it (with png16)
+                # ... and re-encode as bit-depth-16 PNGs under pre_encode_images with encode_format png
+                ("penc16", penc16),
+                ("penc_dynamic", penc_dynamic),  # PNG re-encode: per-image Huffman codes where they make the file shorter
+                ("jenc_optimize", jenc_optimize),  # JPEG re-encode: per-image Huffman tables (libjpeg's optimize_coding rule)
+                # GIF files: the first frame on the logical screen as RGBA8; off: DG_ERR_CORRUPT like any unknown format
+                ("gif", gif),
+                # lossless WebP files: Rgb8 / Rgba8 as the file says; off: DG_ERR_CORRUPT like any unknown format
+                ("webp", webp)):
+            if on:
+                self.set_option(key, 1)
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

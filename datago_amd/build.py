@@ -35,6 +35,7 @@ SOURCES = [
     ("host/png_header.cpp", False),
     ("host/gif_header.cpp", False),
     ("host/webp_header.cpp", False),
+    ("host/options.cpp", False),
     ("host/pipeline.cpp", False),
     ("host/submit.cpp", False),
     ("host/capi.cpp", False),

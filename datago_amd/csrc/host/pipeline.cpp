@@ -70,7 +70,7 @@ Context::Context(int device, const dg_image_config *cfg) : device_(device) {
   } else if (cfg) {
     cfg_ = *cfg;
   }
-  if (cfg) decode_sem_ = cfg->decode_semantics == 1 ? 1 : 0;
+  if (cfg) opt_.decode_sem = cfg->decode_semantics == 1 ? 1 : 0;
 }
 
 Context::~Context() {
@@ -146,7 +146,7 @@ dg_status Context::init() {
     HIPCHK(hipEventCreateWithFlags(&sl.ev_png0, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&sl.ev_png1, hipEventDisableTiming));
   }
-  return make_streams(0, kMaxInflight, slot_queue_, 0, side_queue_);  // the progressive slots' on first use
+  return make_streams(0, kMaxInflight, opt_.slot_queue, 0, opt_.side_queue);  // the progressive slots' on first use
 }
 
 // Streams of the progressive slots (option "prog_queue").  A progressive
@@ -157,7 +157,7 @@ dg_status Context::init() {
 // lowest priority; 3: a CU mask over every CU (a masked stream gets a
 // hardware queue of its own).
 dg_status Context::make_prog_streams() {
-  return make_streams(kMaxInflight, kProgSlots, prog_queue_, prog_cus_, -1);
+  return make_streams(kMaxInflight, kProgSlots, opt_.prog_queue, opt_.prog_cus, -1);
 }
 
 // A slot's streams on first use: the baseline slots past "slots" and the
@@ -167,8 +167,8 @@ dg_status Context::make_prog_streams() {
 dg_status Context::slot_streams(Slot &sl) {
   if (sl.st) return DG_OK;
   const int j = (int)(&sl - slots_);
-  return j < kMaxInflight ? make_streams(j, 1, slot_queue_, 0, side_queue_)
-                          : make_streams(j, 1, prog_queue_, prog_cus_, -1, kAllSlots);
+  return j < kMaxInflight ? make_streams(j, 1, opt_.slot_queue, 0, opt_.side_queue)
+                          : make_streams(j, 1, opt_.prog_queue, opt_.prog_cus, -1, kAllSlots);
 }
 
 // (Re)create the main and side streams of slots [first, first + count):
@@ -180,7 +180,7 @@ dg_status Context::slot_streams(Slot &sl) {
 // Only slots below `limit` (-1: "slots") get streams now; the others on
 // first use (slot_streams).
 dg_status Context::make_streams(int first, int count, int mode, int cus, int side_mode, int limit) {
-  if (limit < 0) limit = nslots_;
+  if (limit < 0) limit = opt_.nslots;
   HIPCHK(hipSetDevice(device_));
   int least = 0, greatest = 0;
   HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -273,530 +273,103 @@ dg_status Context::sync_all() {
 // A rejected option names itself, the value and the accepted range in
 // dg_last_error (the range as the condition that rejects it).
 static dg_status opt_error(const std::string &k, int64_t v, const std::string &why) {
-  set_error("dg_ctx_set_option(\"" + k + "\", " + std::to_string(v) + "): " + why);
+  set_error(option_error_text(k.c_str(), v, why));
   return DG_ERR_INVALID;
 }
 
+// mu_ held: the batches in flight on slots [first, first + count) finish.
+dg_status Context::finish_slots(int first, int count) {
+  for (int j = first; j < first + count; j++) {
+    Slot &sl = slots_[j];
+    if (sl.batch && !sl.batch->done) {
+      dg_status st = finish(sl);
+      if (st) return st;
+    }
+  }
+  return DG_OK;
+}
+
+// The keys, their fields and the values they take are the table in
+// options.cpp (apply_option is its find, check and store in a row); here is
+// what a key does around the store.  A value is checked before anything
+// changes, and a key whose slots must finish first stores once they have.
 dg_status Context::set_option(const std::string &k, int64_t v) {
-  if (k == "sub_bits") {
-    if (v != 0 && (v < 64 || v > 65536 || (v & (v - 1)))) return opt_error(k, v, "valid unless v != 0 && (v < 64 || v > 65536 || (v & (v - 1)))");  // power of two
-    sub_bits_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "sub_auto") {
-    if (v < 1024 || v > 65536 || (v & (v - 1))) return opt_error(k, v, "valid unless v < 1024 || v > 65536 || (v & (v - 1))");
-    sub_auto_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "lead_bits") {
-    if (v < -1 || v > (1 << 20)) return opt_error(k, v, "valid unless v < -1 || v > (1 << 20)");
-    lead_bits_ = v;
-    return DG_OK;
-  }
-  if (k == "coalesce_max") {
-    if (v < 1 || v > 4096) return opt_error(k, v, "valid unless v < 1 || v > 4096");
-    std::lock_guard<std::mutex> lk(cmu_);
-    coalesce_max_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "coalesce_inflight") {  // dg_decode_one: coalesced baseline batches in flight (0 = "slots")
-    if (v < 0 || v > kMaxInflight) return opt_error(k, v, "valid unless v < 0 || v > " + std::to_string(kMaxInflight));
-    std::lock_guard<std::mutex> lk(cmu_);
-    coalesce_inflight_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "coalesce_us") {
-    if (v < 0 || v > 1000000) return opt_error(k, v, "valid unless v < 0 || v > 1000000");
-    std::lock_guard<std::mutex> lk(cmu_);
-    coalesce_us_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "wg_timing") {
-    wg_timing_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "timing") {
-    timing_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "side_stream") {
-    side_stream_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "coef_cache_mb") {  // Lanczos table cache arena (0: off); takes effect at the next reset
-    if (v < 0 || v > 65536) return opt_error(k, v, "valid unless v < 0 || v > 65536");
-    std::lock_guard<std::mutex> lk(mu_);
-    for (const Slot &o : slots_)
-      if (o.batch && !o.batch->done && o.batch->uses_ccache) return opt_error(k, v, "not while a batch in flight uses the table cache");  // not while tables are in use
-    ccache_cap_ = (size_t)v << 20;
-    ccache_clear(true);
-    return DG_OK;
-  }
-  if (k == "entropy_prio") {  // wave issue priority (s_setprio) of the entropy kernels, 0-3
-    if (v < 0 || v > 3) return opt_error(k, v, "valid unless v < 0 || v > 3");
-    entropy_prio_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "max_device_mb") {  // device memory budget of the context (0: none)
-    if (v < 0) return opt_error(k, v, "valid unless v < 0");
-    max_dev_bytes_ = (size_t)v << 20;
-    budget_slots_ = kMaxInflight;
-    budget_planned_ = false;
-    // Contexts under a budget are the ones that share a device (several
-    // ranks, or a loader beside training): their slot streams share the
-    // process's hardware queues instead of taking two of their own each --
-    // 8 ranks x 4 slots x 2 own queues oversubscribed the device's queues
-    // (profiles/r05/ranks: 6-9 Gpx/s at 4 slots, 104 at 2).  An explicit
-    // slot_queue / side_queue wins.
-    if (v > 0 && !queue_set_ && (slot_queue_ != 0 || side_queue_ != -1)) {
-      std::lock_guard<std::mutex> lk(mu_);
-      for (int j = 0; j < kMaxInflight; j++) {
-        Slot &sl = slots_[j];
-        if (sl.batch && !sl.batch->done) {
-          dg_status st = finish(sl);
-          if (st) return st;
-        }
+  const OptRow *r = find_option(k.c_str());
+  if (!r) return opt_error(k, v, "unknown option");
+  if (!option_takes(*r, v)) return opt_error(k, v, r->why);
+  std::unique_lock<std::mutex> lk;  // held through the store and what follows it
+  switch (r->after) {
+    case kAfterCoalesce:
+      lk = std::unique_lock<std::mutex>(cmu_);
+      break;
+    case kAfterCoefCache:
+      lk = std::unique_lock<std::mutex>(mu_);
+      for (const Slot &o : slots_)
+        if (o.batch && !o.batch->done && o.batch->uses_ccache) return opt_error(k, v, "not while a batch in flight uses the table cache");  // not while tables are in use
+      break;
+    case kAfterProgQueue: {
+      {
+        std::lock_guard<std::mutex> plk(pmu_);
+        if (!pagg_.empty()) flush_pagg_locked();
       }
-      slot_queue_ = 0;
-      side_queue_ = -1;
-      bool any = false;
-      for (int j = 0; j < kMaxInflight; j++) any = any || slots_[j].st;
-      if (any) return make_streams(0, kMaxInflight, slot_queue_, 0, side_queue_);
+      lk = std::unique_lock<std::mutex>(mu_);
+      dg_status st = finish_slots(kMaxInflight, kProgSlots);
+      if (st) return st;
+      break;
     }
-    return DG_OK;
-  }
-  if (k == "budget_plan") {  // 1: the first batch under a budget sizes every slot (no growth later); 0: grow and trade
-    budget_plan_ = v != 0;
-    budget_planned_ = false;
-    return DG_OK;
-  }
-  if (k == "slots") {
-    if (v < 1 || v > (int64_t)kMaxInflight) return opt_error(k, v, "valid unless v < 1 || v > " + std::to_string(kMaxInflight));
-    nslots_ = (int)v;
-    next_slot_ %= nslots_;
-    return DG_OK;
-  }
-  if (k == "progressive") {
-    // Progressive JPEGs on the GPU (dg_prog.hip; default on).  A refinement
-    // scan decodes serially in one wave, so a large file takes ~0.1-1 s: the
-    // progressive members of a submission run apart from the rest (prog_split)
-    // in aggregate batches on slots of their own.  0: DG_ERR_UNSUPPORTED (the
-    // caller's CPU decoder takes them).
-    progressive_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "png16") {
-    // 16-bit PNGs on the GPU (default off: DG_ERR_UNSUPPORTED, the caller's CPU
-    // decoder takes them).  1: they decode to native-endian u16 samples
-    // (bit_depth 16), or to RGB8 under image_to_rgb8; a 16-bit image that would
-    // need the resize or an encoder stays DG_ERR_UNSUPPORTED unless "resize16" /
-    // "penc16" take it.
-    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
-    png16_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "gif") {
-    // GIF87a / GIF89a files on the GPU (default off: DG_ERR_CORRUPT like any
-    // format the library does not know).  1: plan_image takes a GIF, its first
-    // frame is LZW-decoded by k_gif_lzw and composited on the logical screen as
-    // Rgba8 by k_gif_expand (dg_gif.hip), what image 0.25's GifDecoder returns
-    // for load_from_memory; from there it is an RGBA8 PNG's pixels.  Stream
-    // irregularities come back DG_ERR_UNSUPPORTED with a dg_last_error text.
-    // dg_probe names a GIF either way and keeps describing the default options.
-    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
-    gif_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "webp") {
-    // Still lossless WebP files (a VP8L image chunk, simple or behind VP8X) on the
-    // GPU (default off: DG_ERR_CORRUPT like any format the library does not
-    // know).  1: plan_image takes the file, k_vp8l_decode reads the bitstream,
-    // k_vp8l_inverse undoes the transforms and k_vp8l_store writes Rgba8 when
-    // the file says it has alpha (the VP8L header's bit, or the VP8X flag of an
-    // extended file) and Rgb8 otherwise (dg_vp8l.hip): what image 0.25's
-    // WebPDecoder returns for load_from_memory.  From there it is an 8-bit RGB /
-    // RGBA PNG's pixels.  Animated and extended lossy files come back
-    // DG_ERR_UNSUPPORTED, a simple lossy file stays an unknown format.
-    // dg_probe names a lossless or extended WebP either way and keeps
-    // describing the default options.
-    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
-    webp_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "jpeg_h1v2") {
-    // Colour JPEGs with a component at the full horizontal and half the
-    // vertical rate (4:4:0, what a lossless 90-degree rotation makes of 4:2:2;
-    // default off: DG_ERR_UNSUPPORTED, the caller's CPU decoder takes them).
-    // 1: parse_jpeg_header accepts them and upsample8 / upsample8_zune blend the
-    // two nearest plane rows 3:1 (kernels.hip).  dg_probe keeps describing the
-    // default options.
-    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
-    jpeg_h1v2_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "jpeg_cmyk") {
-    // Four-component JPEGs with an Adobe APP14 segment of transform 0 (CMYK)
-    // or 2 (YCCK) (default off: DG_ERR_UNSUPPORTED "CMYK/2-component JPEG").
-    // 1: parse_jpeg_header accepts them, the batch's entropy passes run their
-    // four-component instantiations and k_cmyk (kernels.hip) writes the RGB
-    // image that image 0.25 returns for them.  dg_probe keeps describing the
-    // default options.
-    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
-    jpeg_cmyk_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "jpeg_multiscan") {
-    // Three-component sequential JPEGs whose scans carry one or two components
-    // each (non-interleaved; default off: DG_ERR_UNSUPPORTED "non-interleaved
-    // multi-scan JPEG").  1: parse_jpeg_header walks their scans, every scan
-    // becomes an entropy-only descriptor behind the batch's images and the
-    // batch's k_huff_write runs its multiscan instantiation, which stores each
-    // scan's blocks in the image's MCU-interleaved order (ms_index, dg_types.h).
-    // dg_probe keeps describing the default options.
-    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
-    jpeg_multiscan_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "resize16") {
-    // 16-bit PNGs that are not their bucket's size (default off:
-    // DG_ERR_UNSUPPORTED).  1, together with "png16": they resize with the
-    // image crate's resize_to_fill(Lanczos3), which the reference uses for
-    // every non-U8 pixel type (dg_resize16.h); 16-bit into an encoder stays
-    // DG_ERR_UNSUPPORTED unless "penc16" is on.
-    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
-    resize16_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "penc16") {
-    // 16-bit PNGs into the PNG re-encoder (default off: DG_ERR_UNSUPPORTED).  1,
-    // together with "png16" (and "resize16" for an image that is not its
-    // bucket's size): under pre_encode_images with encode_format png the
-    // transformed samples come back as a bit-depth-16 PNG, as the reference's
-    // PngEncoder writes an ImageLuma16 / LumaA16 / Rgb16 / Rgba16
-    // (k_penc_filter16, dg_penc16.h).  The JPEG encoder takes 8-bit samples
-    // only.  8-bit images and image_to_rgb8 contexts are untouched.
-    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
-    penc16_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "penc_dynamic") {
-    // PNG re-encode (pre_encode_images, encode_format png): 1 = an image whose
-    // DEFLATE block is strictly shorter under a Huffman code built from its own
-    // histogram takes a dynamic block (dg_penc_tree.h); every other image, and
-    // every image with 0 (the default), takes the fixed block byte for byte as
-    // before.  Nothing changes for JPEG re-encoding.
-    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
-    penc_dynamic_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "jenc_optimize") {
-    // JPEG re-encode (pre_encode_images, encode_format jpeg): 1 = every image is
-    // coded with Huffman tables built from its own symbol counts by libjpeg's
-    // jpeg_gen_optimal_table rule (dg_jenc_tree.h) and carries them in its DHT
-    // segments; everything else in the file is unchanged.  An image in which
-    // the rule meets a code size above 32, and every image with 0 (the
-    // default), takes the Annex K tables byte for byte as before.  Nothing
-    // changes for PNG re-encoding.
-    if (v < 0 || v > 1) return opt_error(k, v, "valid unless v < 0 || v > 1");
-    jenc_optimize_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "prog_lanes") {  // dg_decode_one: progressive batches in flight on the progressive slots; 0: mixed in
-    if (v < 0 || v > kProgSlots) return opt_error(k, v, "valid unless v < 0 || v > " + std::to_string(kProgSlots));
-    prog_lanes_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "prog_queue") {  // progressive slots' streams: 0 plain, 1 high / 2 low priority, 3 CU-masked
-    if (v < 0 || v > 3) return opt_error(k, v, "valid unless v < 0 || v > 3");
-    {
-      std::lock_guard<std::mutex> lk(pmu_);
-      if (!pagg_.empty()) flush_pagg_locked();
+    case kAfterSlotQueue: {
+      queue_set_ = true;
+      lk = std::unique_lock<std::mutex>(mu_);
+      dg_status st = finish_slots(0, kMaxInflight);
+      if (st) return st;
+      break;
     }
-    std::lock_guard<std::mutex> lk(mu_);
-    for (int j = 0; j < kProgSlots; j++) {
-      Slot &sl = slots_[kMaxInflight + j];
-      if (sl.batch && !sl.batch->done) {
-        dg_status st = finish(sl);
+    default:
+      break;
+  }
+  store_option(*r, opt_, v);
+  switch (r->after) {
+    case kAfterCoefCache:
+      ccache_clear(true);
+      break;
+    case kAfterMaxDevice:
+      budget_slots_ = kMaxInflight;
+      budget_planned_ = false;
+      // Contexts under a budget are the ones that share a device (several
+      // ranks, or a loader beside training): their slot streams share the
+      // process's hardware queues instead of taking two of their own each --
+      // 8 ranks x 4 slots x 2 own queues oversubscribed the device's queues
+      // (profiles/r05/ranks: 6-9 Gpx/s at 4 slots, 104 at 2).  An explicit
+      // slot_queue / side_queue wins.
+      if (v > 0 && !queue_set_ && (opt_.slot_queue != 0 || opt_.side_queue != -1)) {
+        lk = std::unique_lock<std::mutex>(mu_);
+        dg_status st = finish_slots(0, kMaxInflight);
         if (st) return st;
+        opt_.slot_queue = 0;
+        opt_.side_queue = -1;
+        bool any = false;
+        for (int j = 0; j < kMaxInflight; j++) any = any || slots_[j].st;
+        if (any) return make_streams(0, kMaxInflight, opt_.slot_queue, 0, opt_.side_queue);
       }
-    }
-    prog_queue_ = (int)v;
-    return make_prog_streams();
+      break;
+    case kAfterBudgetPlan:
+      budget_planned_ = false;
+      break;
+    case kAfterSlots:
+      next_slot_ %= opt_.nslots;
+      break;
+    case kAfterProgQueue:
+      return make_prog_streams();
+    case kAfterSlotQueue:
+      return make_streams(0, kMaxInflight, opt_.slot_queue, 0, opt_.side_queue);
+    case kAfterResetHostUs:
+      for (double &x : host_us_) x = 0;
+      for (double &x : host_cpu_us_) x = 0;
+      break;
+    default:
+      break;
   }
-  if (k == "slot_queue") {  // baseline slots' streams: 0 plain, 1 high / 2 low priority, 3 CU-masked (own queues)
-    if (v < 0 || v > 3) return opt_error(k, v, "valid unless v < 0 || v > 3");
-    queue_set_ = true;
-    std::lock_guard<std::mutex> lk(mu_);
-    for (int j = 0; j < kMaxInflight; j++) {
-      Slot &sl = slots_[j];
-      if (sl.batch && !sl.batch->done) {
-        dg_status st = finish(sl);
-        if (st) return st;
-      }
-    }
-    slot_queue_ = (int)v;
-    return make_streams(0, kMaxInflight, slot_queue_, 0, side_queue_);
-  }
-  if (k == "side_queue") {  // the baseline slots' side streams: -1 as slot_queue, else a slot_queue mode
-    if (v < -1 || v > 3) return opt_error(k, v, "valid unless v < -1 || v > 3");
-    queue_set_ = true;
-    std::lock_guard<std::mutex> lk(mu_);
-    for (int j = 0; j < kMaxInflight; j++) {
-      Slot &sl = slots_[j];
-      if (sl.batch && !sl.batch->done) {
-        dg_status st = finish(sl);
-        if (st) return st;
-      }
-    }
-    side_queue_ = (int)v;
-    return make_streams(0, kMaxInflight, slot_queue_, 0, side_queue_);
-  }
-  if (k == "prog_cus") {  // prog_queue 3: CUs the progressive streams may use (0 = all); set before prog_queue
-    if (v < 0 || v > 4096) return opt_error(k, v, "valid unless v < 0 || v > 4096");
-    prog_cus_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "prog_split") {  // dg_submit: progressive members into the progressive aggregate (0: decoded in the batch)
-    prog_split_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "prog_batch") {  // progressive aggregate: launched once it holds this many images
-    if (v < 1 || v > 65536) return opt_error(k, v, "valid unless v < 1 || v > 65536");
-    prog_batch_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "prog_flush_us") {  // ... or once it is this old at a submit / poll / wait_ready
-    if (v < 0 || v > 100000000) return opt_error(k, v, "valid unless v < 0 || v > 100000000");
-    prog_flush_us_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "sync2") {  // k_huff_sync2: two lead-in + range chains per lane (0: one, k_huff_sync)
-    sync2_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "sync_pair") {  // k_huff_sync: a second AC symbol per single step from the same peek (A/B)
-    sync_pair_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "sync_chain") {  // k_huff_sync: up to v more multi entries per state-only step from the same peek (0..3)
-    if (v < 0 || v > 3) return opt_error(k, v, "valid unless v < 0 || v > 3");
-    sync_chain_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "write_pair") {  // k_huff_write: up to v more AC symbols per step from the same peek (0..3)
-    if (v < 0 || v > 3) return opt_error(k, v, "valid unless v < 0 || v > 3");
-    write_pair_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "multi_lead") {  // multi-symbol AC steps in k_huff_sync's lead-in (A/B)
-    multi_lead_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "prog_side") {  // progressive scans on the side stream, beside the baseline entropy decode
-    prog_side_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "prog_chain") {  // chain dependency groups costing <= this % of the batch's longest scan (0: off)
-    if (v < 0 || v > 100000) return opt_error(k, v, "valid unless v < 0 || v > 100000");
-    prog_chain_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "prog_pipe") {  // 0: one k_prog_scan launch per level (A/B)
-    prog_pipe_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "prog_serial") {  // every progressive scan on the serial reader (A/B; restart scans always are)
-    prog_serial_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "entropy_once") {  // decode-once: k_huff_sync stages coefficients, k_huff_scatter writes them
-    entropy_once_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "entropy_lpt") {
-    entropy_lpt_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "hb_bands") {  // band H kernel: 8-row bands per workgroup
-    if (v < 1 || v > 64) return opt_error(k, v, "valid unless v < 1 || v > 64");
-    hb_bands_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "idct_fused") {  // IDCT inside k_huff_write's block flush (default 0: measured slower)
-    idct_fused_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "idct_thread") {
-    idct_thread_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "sparse_coef") {
-    sparse_coef_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "h_prefetch") {
-    h_prefetch_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "h_planar") {
-    h_planar_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "destuff_one") {
-    destuff_one_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "chroma_rec") {
-    chroma_rec_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "reset_host_us") {  // zero the host_us_* / host_cpu_us_* stats
-    for (double &x : host_us_) x = 0;
-    for (double &x : host_cpu_us_) x = 0;
-    return DG_OK;
-  }
-  if (k == "hv_fused") {  // fused first H + V pass of colour JPEGs where it fits (default 0: slower)
-    hv_fused_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "copy_threads") {  // host threads for the output copies of a host-out batch (default 8)
-    if (v < 1 || v > 64) return opt_error(k, v, "valid unless v < 1 || v > 64");
-    copy_threads_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "ckpt") {  // entropy checkpoints for early merging of re-decodes (default 1)
-    ckpt_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "decode_semantics") {  // 0: libjpeg-turbo (pinned), 1: zune-jpeg 0.5.12 restated (unpinned)
-    if (v != 0 && v != 1) return opt_error(k, v, "valid unless v != 0 && v != 1");
-    decode_sem_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "small_coded") {  // batches under this many coded bytes take sub_small / lead_small (0 = off)
-    if (v < 0) return opt_error(k, v, "valid unless v < 0");
-    small_coded_ = (uint64_t)v;
-    return DG_OK;
-  }
-  if (k == "sub_small") {
-    if (v < 64 || v > 65536 || (v & (v - 1))) return opt_error(k, v, "valid unless v < 64 || v > 65536 || (v & (v - 1))");
-    sub_small_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "lead_small") {
-    if (v < 0 || v > (1 << 16)) return opt_error(k, v, "valid unless v < 0 || v > (1 << 16)");
-    lead_small_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "v_tile") {  // V pass output rows per column tile (k_resize_vt); 0: one thread per 16 output bytes
-    if (v != 0 && v != 2 && v != 4 && v != 8) return opt_error(k, v, "valid: 0, 2, 4, 8");
-    v_tile_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "v_units") {  // k_resize_v: 256-unit strides per workgroup item
-    if (v < 1 || v > 8) return opt_error(k, v, "valid unless v < 1 || v > 8");
-    v_units_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "lead_big") {  // auto lead-in of images with >= 4-block MCUs (4:2:0), bits
-    if (v < 0 || v > (1 << 16)) return opt_error(k, v, "valid unless v < 0 || v > (1 << 16)");
-    lead_big_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "write_split") {  // 1: k_huff_write decodes each range as two halves (see k_huff_write)
-    write_split_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "meta_pull") {  // the GPU reads from page-locked staging: 1 the descriptors, 2 also host inputs
-    if (v < 0 || v > 2) return opt_error(k, v, "valid unless v < 0 || v > 2");
-    meta_pull_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "plan_threads") {  // host threads parsing a submission's headers (1 = the caller only)
-    if (v < 1 || v > 64) return opt_error(k, v, "valid unless v < 1 || v > 64");
-    plan_threads_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "inf_stage3") {  // k_inf_find: Kraft survivors queued per full header check round
-    if (v != 8 && v != 16 && v != 32 && v != 64) return opt_error(k, v, "valid unless v != 8 && v != 16 && v != 32 && v != 64");
-    inf_stage3_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "inf_cap") {  // chunk-parallel inflate: entries per chunk, in tenths of the image's expansion of a span
-    if (v < 10 || v > 100) return opt_error(k, v, "valid unless v < 10 || v > 100");
-    inf_cap_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "png_alias") {  // PNG chunk entries share device memory with the later stages' buffers
-    png_alias_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "inf_pad") {  // chunk-parallel inflate: entries per chunk on top of inf_cap's
-    if (v < 0 || v > (1 << 20)) return opt_error(k, v, "valid unless v < 0 || v > 2^20");
-    inf_pad_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "inf_chunk") {  // compressed bytes per chunk of the chunk-parallel inflate
-    if (v < 4096 || v > 65536 || (v & (v - 1))) return opt_error(k, v, "valid unless v < 4096 || v > 65536 || (v & (v - 1))");
-    inf_chunk_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "png_chunked") {  // 0: every PNG inflates serially (test switch)
-    chunked_off_ = v == 0;
-    return DG_OK;
-  }
-  if (k == "lead_density") {
-    lead_density_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "sub_density") {  // bits-per-block threshold for shorter subsequences (0 = off)
-    if (v < 0 || v > 4096) return opt_error(k, v, "valid unless v < 0 || v > 4096");
-    sub_density_ = (double)v;
-    return DG_OK;
-  }
-  if (k == "uf_per_cu") {  // PNG unfilter: persistent workers per CU at most (0: as many as the LDS holds)
-    if (v < 0 || v > 16) return opt_error(k, v, "valid unless v < 0 || v > 16");
-    uf_per_cu_ = (int)v;
-    return DG_OK;
-  }
-  if (k == "uf_units") {  // PNG unfilter: filter units per lane per step (1: half the LDS per worker)
-    if (v < 1 || v > 2) return opt_error(k, v, "valid unless v < 1 || v > 2");
-    uf_units_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "inf_decode") {  // k_inf_decode lookup bits (literal/length, distance): 0 9/7, 1 8/6, 2 7/6, 3 7/5, 4 6/5,
-                            // 5 6/4; 6, 7 = 2, 1 with the wave-batched register stream buffer; 8 / 9 / 11 =
-                            // 7/6, 6/5, 8/6 with the canonical walk's symbol tables in LDS; 12 / 13 = 8 / 9
-                            // with the register buffer; 14 = 0 with it, 15 = 11 with it; 16 = 3 with it;
-                            // 17 7/4, 18 8/5, 19 8/4; 20 / 21 / 22 = 17 / 4 / 5 with the register buffer;
-                            // 23 / 24 / 25 / 26 / 27 = 16 with a 4 / 12 / 16 / 24 / 32-word buffer;
-                            // 28 = 20 with a 16-word buffer
-    if (v < 0 || v > 28 || v == 10) return opt_error(k, v, "valid unless v < 0 || v > 28 || v == 10");
-    inf_decode_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "h_mfma") {  // 0: band H passes with the VALU convolution (k_resize_hb, A/B)
-    h_mfma_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "band_dec") {  // 0: IDCT to planes + band H kernel (the split path, A/B)
-    band_dec_ = v != 0;
-    return DG_OK;
-  }
-  if (k == "dec_dbg") {  // timing experiments: skip k_band_dec phases (wrong pixels)
-    dec_dbg_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "dec_strips") {
-    if (v < 1 || v > 4096) return opt_error(k, v, "valid unless v < 1 || v > 4096");
-    dec_strips_ = (uint32_t)v;
-    return DG_OK;
-  }
-  if (k == "debug_flags") {
-    debug_flags_ = (int)v;
-    return DG_OK;
-  }
-  return opt_error(k, v, "unknown option");
+  return DG_OK;
 }
 
 int64_t Context::get_stat(const std::string &k) {
@@ -813,7 +386,7 @@ int64_t Context::get_stat(const std::string &k) {
   if (k == "prog_chains") return stat_prog_chains_;
   if (k == "pool_flushes") return stat_pool_flush_;
   if (k == "sync_iters_max") return stat_iters_;
-  if (k == "sync_chain") return sync_chain_;
+  if (k == "sync_chain") return opt_.sync_chain;
   {  // wg_timing summaries, in nanoseconds: wg_{sync,write}_{span,mean,p90,max}
     static const char *kn[2] = {"sync", "write"}, *sn[4] = {"span", "mean", "p90", "max"};
     for (int a = 0; a < 2; a++)
@@ -821,8 +394,8 @@ int64_t Context::get_stat(const std::string &k) {
         if (k == std::string("wg_") + kn[a] + "_" + sn[q]) return (int64_t)(wgstat_[a][q] * 1000.0);
   }
   if (k == "sub_bits") return last_sub_bits_;
-  if (k == "sub_auto") return sub_auto_;
-  if (k == "coalesce_inflight") return coalesce_inflight_;
+  if (k == "sub_auto") return opt_.sub_auto;
+  if (k == "coalesce_inflight") return opt_.coalesce_inflight;
   if (k == "meta_bytes") return (int64_t)last_meta_bytes_;
   if (k == "allocs") return stat_allocs_;
   if (k == "alloc_mb") return stat_alloc_mb_;
@@ -833,10 +406,10 @@ int64_t Context::get_stat(const std::string &k) {
     std::lock_guard<std::mutex> lk(mu_);
     return (int64_t)(dev_footprint() >> 20);
   }
-  if (k == "max_device_mb") return (int64_t)(max_dev_bytes_ >> 20);
+  if (k == "max_device_mb") return (int64_t)(opt_.max_dev_bytes >> 20);
   if (k == "budget_splits") return stat_budget_splits_;
   if (k == "budget_plan_mb") return (int64_t)(plan_arena_ >> 20);  // planned bytes per slot
-  if (k == "budget_slots") return max_dev_bytes_ ? std::min<int64_t>(nslots_, stat_budget_slots_min_) : nslots_;
+  if (k == "budget_slots") return opt_.max_dev_bytes ? std::min<int64_t>(opt_.nslots, stat_budget_slots_min_) : opt_.nslots;
   if (k == "coef_cache_hits") return stat_ccache_hits_;
   if (k == "coef_cache_new") return stat_ccache_new_;
   if (k == "coef_cache_resets") return stat_ccache_resets_;
@@ -945,7 +518,7 @@ dg_status Context::ensure(DevBuf &b, size_t bytes, hipStream_t user, bool exact)
   (void)user;
   if (b.cap >= bytes) return DG_OK;
   if (b.p) {
-    if (max_dev_bytes_) {  // under a budget the old buffer is gone now (budget_fit counted it so)
+    if (opt_.max_dev_bytes) {  // under a budget the old buffer is gone now (budget_fit counted it so)
       hipFree(b.p);
     } else {
       retire(b.p, b.cap, false);
@@ -967,7 +540,7 @@ dg_status Context::ensure(DevBuf &b, size_t bytes, hipStream_t user, bool exact)
   size_t dfree = 0, dtotal = 0;
   const bool roomy = hipMemGetInfo(&dfree, &dtotal) != hipSuccess || dfree > dtotal / 4 + bytes;
   size_t cap = exact ? align_up(bytes, (size_t)1 << 20) : grow_cap(bytes, roomy);
-  if (max_dev_bytes_) {
+  if (opt_.max_dev_bytes) {
     const size_t lim = align_up(bytes, 1 << 20) + (budget_room_ / 3 & ~(((size_t)1 << 20) - 1));
     cap = std::min(cap, std::max(lim, align_up(bytes, 1 << 20)));
     budget_room_ -= std::min(budget_room_, cap - std::min(cap, bytes));
@@ -1012,7 +585,7 @@ size_t Context::dev_footprint(const Slot *except) const {
 // writes it (finishing them first, as a pool flush does).  Runs before a
 // batch's lookups, so a batch never mixes entries of two arena lifetimes.
 void Context::ccache_maybe_reset(Slot &self) {
-  if (!ccache_cap_ || (!ccache_full_ && ccache_off_ <= ccache_cap_ / 8 * 7)) return;
+  if (!opt_.ccache_cap || (!ccache_full_ && ccache_off_ <= opt_.ccache_cap / 8 * 7)) return;
   for (Slot &o : slots_) {
     if (&o == &self || !o.batch || o.batch->done || !o.batch->uses_ccache) continue;
     if (finish(o)) return;  // keep the arena as it is; the next batch tries again
@@ -1061,7 +634,7 @@ void Context::ccache_rollback(size_t n0, size_t off0) {
 
 int Context::ccache_lookup(const ResizePass &ps, Batch &b, bool &hit) {
   hit = false;
-  if (!ccache_cap_ || max_dev_bytes_ && ccache_cap_ > max_dev_bytes_ / 8) return -1;
+  if (!opt_.ccache_cap || opt_.max_dev_bytes && opt_.ccache_cap > opt_.max_dev_bytes / 8) return -1;
   CKey k;
   memcpy(&k.in0, &ps.in0, 8);
   memcpy(&k.in1, &ps.in1, 8);
@@ -1080,18 +653,18 @@ int Context::ccache_lookup(const ResizePass &ps, Batch &b, bool &hit) {
   }
   const size_t bytes = align_up((size_t)ps.out_size * 8 + (size_t)ps.out_size * ps.ksize * 2, 256);
   // full (arena, or the index at 3/4 load): the next submit starts the arena over
-  if (ccache_off_ + bytes > ccache_cap_ || ccache_.size() >= ((size_t)3 << kCIdxBits) / 4) {
+  if (ccache_off_ + bytes > opt_.ccache_cap || ccache_.size() >= ((size_t)3 << kCIdxBits) / 4) {
     ccache_full_ = true;
     return -1;
   }
   if (!d_ccache_.p) {
-    if (hipMalloc(&d_ccache_.p, ccache_cap_) != hipSuccess) {
+    if (hipMalloc(&d_ccache_.p, opt_.ccache_cap) != hipSuccess) {
       (void)hipGetLastError();
       d_ccache_.p = nullptr;
-      ccache_cap_ = 0;  // no cache on this device
+      opt_.ccache_cap = 0;  // no cache on this device
       return -1;
     }
-    d_ccache_.cap = ccache_cap_;
+    d_ccache_.cap = opt_.ccache_cap;
   }
   const int idx = (int)ccache_.size();
   ccache_.push_back(CEntry{k, ccache_off_, 0, false});
@@ -1143,13 +716,13 @@ dg_status Context::budget_planned_fit(Slot &sl, size_t rs, size_t rc, size_t ri)
     sl.input = DevBuf{ri ? a + oi : nullptr, ri};
     sl.views = true;
     const size_t fp = dev_footprint();
-    budget_room_ = fp < max_dev_bytes_ ? (max_dev_bytes_ - fp) / 2 : 0;
+    budget_room_ = fp < opt_.max_dev_bytes ? (opt_.max_dev_bytes - fp) / 2 : 0;
   };
   if (budget_planned_) {
     if (need > plan_arena_) return kNeedSplit;
     if (!sl.arena.p) {  // a planned slot without its arena (a progressive batch took the room): take it back
       if (sl.scratch.p || sl.coef.p || sl.input.p) free_slot_buffers(sl);
-      if (dev_footprint() + plan_arena_ > max_dev_bytes_ || ensure(sl.arena, plan_arena_, sl.st, true))
+      if (dev_footprint() + plan_arena_ > opt_.max_dev_bytes || ensure(sl.arena, plan_arena_, sl.st, true))
         return kNeedSplit;
     }
     carve();
@@ -1166,17 +739,17 @@ dg_status Context::budget_planned_fit(Slot &sl, size_t rs, size_t rc, size_t ri)
   free_slot_buffers(sl);
   if (!retired_dev_.empty() && sync_all() == DG_OK) free_retired();
   const size_t others = dev_footprint(&sl) + sl.meta.cap + sl.wgt.cap;
-  if (others >= max_dev_bytes_) return kNeedSplit;
+  if (others >= opt_.max_dev_bytes) return kNeedSplit;
   // descriptor / weight buffers of the planned slots grow into the reserve
   const size_t reserve =
-      std::min<size_t>(std::max<size_t>(max_dev_bytes_ / 32, 64 * MB), (max_dev_bytes_ - others) / 4);
-  size_t avail = max_dev_bytes_ - others - reserve;
+      std::min<size_t>(std::max<size_t>(opt_.max_dev_bytes / 32, 64 * MB), (opt_.max_dev_bytes - others) / 4);
+  size_t avail = opt_.max_dev_bytes - others - reserve;
   {  // a budget above what the device has free plans for what it has (less 1/8 for the others on it)
     size_t dfree = 0, dtotal = 0;
     if (hipMemGetInfo(&dfree, &dtotal) == hipSuccess) avail = std::min(avail, dfree - std::min(dfree, dtotal / 8));
   }
   if (need + need / 4 > avail) return kNeedSplit;  // the halves plan the budget
-  const int ns = (int)std::max<size_t>(1, std::min<size_t>((size_t)nslots_, avail / (need + need / 4)));
+  const int ns = (int)std::max<size_t>(1, std::min<size_t>((size_t)opt_.nslots, avail / (need + need / 4)));
   plan_arena_ = (avail / (size_t)ns) & ~(MB - 1);
   if (ensure(sl.arena, plan_arena_, sl.st, true)) {
     set_error("device allocation of the planned budget failed");
@@ -1208,7 +781,7 @@ dg_status Context::budget_planned_fit(Slot &sl, size_t rs, size_t rc, size_t ri)
 // check.)
 bool Context::budget_fit(Slot &self, size_t rs, size_t rc, size_t ri) {
   budget_room_ = 0;
-  if (!max_dev_bytes_) return true;
+  if (!opt_.max_dev_bytes) return true;
   const size_t fixed = self.meta.cap + self.wgt.cap;
   const size_t keep = std::max(self.scratch.cap, rs) + std::max(self.coef.cap, rc) + std::max(self.input.cap, ri) + fixed;
   const size_t tight = rs + rc + ri + fixed;
@@ -1219,22 +792,22 @@ bool Context::budget_fit(Slot &self, size_t rs, size_t rc, size_t ri) {
     free_slot_buffers(o);
   };
   auto has_buffers = [](const Slot &o) { return o.scratch.p || o.coef.p || o.input.p || o.arena.p; };
-  if (others() + keep > max_dev_bytes_ && !retired_dev_.empty() && sync_all() == DG_OK) free_retired();
+  if (others() + keep > opt_.max_dev_bytes && !retired_dev_.empty() && sync_all() == DG_OK) free_retired();
   if (budget_planned_) {  // (a progressive slot) the planned baseline slots keep their buffers
-    for (int j = kMaxInflight; j < kAllSlots && others() + keep > max_dev_bytes_; j++)
+    for (int j = kMaxInflight; j < kAllSlots && others() + keep > opt_.max_dev_bytes; j++)
       if (j != si) give_back(slots_[j]);
-    if (others() + keep <= max_dev_bytes_) {
-      budget_room_ = max_dev_bytes_ - others() - keep;
+    if (others() + keep <= opt_.max_dev_bytes) {
+      budget_room_ = opt_.max_dev_bytes - others() - keep;
       return true;
     }
-    if (others() + tight > max_dev_bytes_) return false;
+    if (others() + tight > opt_.max_dev_bytes) return false;
     free_slot_buffers(self);
-    budget_room_ = max_dev_bytes_ - others() - tight;
+    budget_room_ = opt_.max_dev_bytes - others() - tight;
     return true;
   }
-  for (int j = std::max(1, budget_slots_); j < kMaxInflight && others() + keep > max_dev_bytes_; j++)
+  for (int j = std::max(1, budget_slots_); j < kMaxInflight && others() + keep > opt_.max_dev_bytes; j++)
     if (j != si && has_buffers(slots_[j])) give_back(slots_[j]);
-  while (others() + keep > max_dev_bytes_) {
+  while (others() + keep > opt_.max_dev_bytes) {
     int j = kMaxInflight - 1;
     while (j >= 0 && (j == si || !has_buffers(slots_[j]))) j--;
     if (j < 0) break;
@@ -1243,15 +816,15 @@ bool Context::budget_fit(Slot &self, size_t rs, size_t rc, size_t ri) {
     budget_slots_ = std::max(1, std::min(budget_slots_, std::max(j, si + 1)));
     stat_budget_slots_min_ = std::min<int64_t>(stat_budget_slots_min_, budget_slots_);
   }
-  for (int j = kMaxInflight; j < kAllSlots && others() + keep > max_dev_bytes_; j++)
+  for (int j = kMaxInflight; j < kAllSlots && others() + keep > opt_.max_dev_bytes; j++)
     if (j != si) give_back(slots_[j]);
-  if (others() + keep <= max_dev_bytes_) {
-    budget_room_ = max_dev_bytes_ - others() - keep;
+  if (others() + keep <= opt_.max_dev_bytes) {
+    budget_room_ = opt_.max_dev_bytes - others() - keep;
     return true;
   }
-  if (others() + tight > max_dev_bytes_) return false;
+  if (others() + tight > opt_.max_dev_bytes) return false;
   free_slot_buffers(self);
-  budget_room_ = max_dev_bytes_ - others() - tight;
+  budget_room_ = opt_.max_dev_bytes - others() - tight;
   return true;
 }
 
@@ -1450,7 +1023,7 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
   uint32_t W, H, C;
   if (is_png(h, len)) {
     p.fmt = kFmtPng;
-    parse_png_header(h, len, p.png, png16_);
+    parse_png_header(h, len, p.png, opt_.png16);
     if (p.png.status != PH_OK) {
       p.status = p.png.status == PH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
       return DG_OK;
@@ -1467,7 +1040,7 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     W = p.png.width;
     H = p.png.height;
     C = (uint32_t)p.png.out_c;
-  } else if (gif_ && is_gif(h, len)) {  // option "gif"
+  } else if (opt_.gif && is_gif(h, len)) {  // option "gif"
     p.fmt = kFmtGif;
     parse_gif_header(h, len, p.gif);
     if (p.gif.status != GH_OK) {
@@ -1484,7 +1057,7 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     W = p.gif.width;
     H = p.gif.height;
     C = 4;
-  } else if (webp_ && is_webp(h, len)) {  // option "webp"
+  } else if (opt_.webp && is_webp(h, len)) {  // option "webp"
     p.fmt = kFmtWebp;
     parse_webp_header(h, len, p.webp);
     if (p.webp.status != WH_OK) {
@@ -1506,17 +1079,17 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
       return DG_OK;
     }
     // options "jpeg_h1v2", "jpeg_cmyk", "jpeg_multiscan"
-    parse_jpeg_header(h, len, p.hdr, jpeg_h1v2_, jpeg_cmyk_, jpeg_multiscan_);
+    parse_jpeg_header(h, len, p.hdr, opt_.jpeg_h1v2, opt_.jpeg_cmyk, opt_.jpeg_multiscan);
     if (p.hdr.status != JH_OK) {
       p.status = p.hdr.status == JH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
       return DG_OK;
     }
-    if (p.hdr.progressive && !progressive_) {  // see option "progressive"
+    if (p.hdr.progressive && !opt_.progressive) {  // see option "progressive"
       p.hdr.why = "progressive JPEG (context option \"progressive\" decodes it on the GPU)";
       p.status = DG_ERR_UNSUPPORTED;
       return DG_OK;
     }
-    if (p.hdr.incomplete_refinement && decode_sem_ == 0) {
+    if (p.hdr.incomplete_refinement && opt_.decode_sem == 0) {
       // libjpeg-turbo would smooth these blocks (jdcoefct.c smoothing_ok); zune-jpeg does not
       p.hdr.why = "incomplete progressive refinement (libjpeg block smoothing; decodes with decode_semantics 1)";
       p.status = DG_ERR_UNSUPPORTED;
@@ -1558,7 +1131,7 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
   if (deep && has_cfg_ && !(W == ow && H == oh)) {
     // the reference resizes non-U8 pixel types with image's own f32 Lanczos3
     // (resize_to_fill), not the fast_image_resize path restated here
-    if (!resize16_) {
+    if (!opt_.resize16) {
       p.png.why = "PNG: 16-bit resize (only a 16-bit image of its bucket's size decodes on the GPU)";
       p.status = DG_ERR_UNSUPPORTED;
       return DG_OK;
@@ -1569,7 +1142,7 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     }
   }
   const bool deep_enc = deep && cfg_.pre_encode_images && !cfg_.image_to_rgb8;  // 16-bit samples at an encoder
-  if (deep_enc && !penc16_) {
+  if (deep_enc && !opt_.penc16) {
     p.png.why = "PNG: 16-bit image to an encoder (the GPU encoders take 8-bit samples)";
     p.status = DG_ERR_UNSUPPORTED;
     return DG_OK;
@@ -1617,7 +1190,7 @@ dg_status Context::output_size(const uint8_t *bytes, size_t len, int32_t forced,
 // first timed window: 110 vs 115-117 Gpx/s in the other four windows).
 void Context::prewarm_slots(const Slot &self) {
   if (&self - slots_ >= kMaxInflight) return;
-  const int ns = max_dev_bytes_ ? std::max(1, std::min(nslots_, budget_slots_)) : nslots_;
+  const int ns = opt_.max_dev_bytes ? std::max(1, std::min(opt_.nslots, budget_slots_)) : opt_.nslots;
   for (int j = 0; j < ns; j++) {
     Slot &o = slots_[j];
     if (&o == &self || (o.batch && !o.batch->done)) continue;
@@ -1643,11 +1216,11 @@ void Context::prewarm_slots(const Slot &self) {
 int Context::pick_slot() {
   // the planned budget's first sizing runs on slot 0 (budget_planned_fit sizes
   // slots [0, budget_slots_)); submissions split before it keep that slot
-  if (max_dev_bytes_ && budget_plan_ && !budget_planned_) {
+  if (opt_.max_dev_bytes && opt_.budget_plan && !budget_planned_) {
     next_slot_ = 0;
     return 0;
   }
-  const int ns = max_dev_bytes_ ? std::max(1, std::min(nslots_, budget_slots_)) : nslots_;
+  const int ns = opt_.max_dev_bytes ? std::max(1, std::min(opt_.nslots, budget_slots_)) : opt_.nslots;
   const int i = next_slot_ % ns;
   next_slot_ = (i + 1) % ns;
   return i;
@@ -1750,14 +1323,14 @@ void Context::plan_prog_items(Batch &b) {
     g.cost += cost[j];
     g.dc |= (sc.ss == 0 && sc.ah == 0 ? sc.ns : (sc.ss == 0 ? 0u : 1u)) > 1;
   }
-  const double limit = longest * (double)prog_chain_ / 100.0;
+  const double limit = longest * (double)opt_.prog_chain / 100.0;
   std::vector<uint32_t> split[2];            // pipelined scans, AC / DC launch
   std::vector<std::pair<double, uint32_t>> chains[2];  // (cost, group)
   std::vector<double> img_cost(b.descs.size(), 0.0);
   for (uint32_t j = 0; j < n; j++) img_cost[b.pscans[j].image] += cost[j];
   for (uint32_t g = 0; g < (uint32_t)groups.size(); g++) {
     Group &G = groups[g];
-    if ((prog_chain_ > 0 && G.cost <= limit) || nodeps[b.pscans[G.scans[0]].image]) {
+    if ((opt_.prog_chain > 0 && G.cost <= limit) || nodeps[b.pscans[G.scans[0]].image]) {
       for (size_t i = 0; i < G.scans.size(); i++) {
         ProgScan &sc = b.pscans[G.scans[i]];
         sc.pflags |= kProgChained;
@@ -1805,7 +1378,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   auto lst = [&](int l) { return (const WgItem *)(M + b.list_off[l]); };
   auto cnt = [&](int l) { return (uint32_t)b.lists[l].size(); };
   auto ev = [&](int i) -> dg_status {
-    if (timing_) HIPCHK(hipEventRecord(sl.ev[i], sl.st));
+    if (opt_.timing) HIPCHK(hipEventRecord(sl.ev[i], sl.st));
     return DG_OK;
   };
   if (from_fix) HIPCHK(hipMemsetAsync(fl, 0, kFlagCounters, sl.st));
@@ -1816,11 +1389,11 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   const int alpha_flags = from_fix ? 1 : 0;
   if (next()) return DG_ERR_DEVICE;
   if (!from_fix && cnt(L_R16T)) {  // 16-bit resize: tap tables depend only on the plan (beside the inflate / unfilter)
-    if (side_stream_) {
+    if (opt_.side_stream) {
       HIPCHK(hipEventRecord(sl.ev_meta, sl.st));
       HIPCHK(hipStreamWaitEvent(sl.side, sl.ev_meta, 0));
     }
-    launch_r16_taps(side_stream_ ? sl.side : sl.st, dd, lst(L_R16T), cnt(L_R16T));
+    launch_r16_taps(opt_.side_stream ? sl.side : sl.st, dd, lst(L_R16T), cnt(L_R16T));
   }
   if (!from_fix && b.any_png) {
     launch_png_gather(sl.st, (const GatherJob *)(M + b.gjob_off), lst(L_GATHER), cnt(L_GATHER));
@@ -1828,7 +1401,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
       // streams too small to chunk (masks) inflate serially on the side stream,
       // beside the chunked kernels (which leave most CUs idle); chunked images
       // the resolve gives up on follow on the main stream
-      const bool beside = side_stream_;
+      const bool beside = opt_.side_stream;
       if (beside) {
         HIPCHK(hipEventRecord(sl.ev_png0, sl.st));
         HIPCHK(hipStreamWaitEvent(sl.side, sl.ev_png0, 0));
@@ -1836,8 +1409,8 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
         HIPCHK(hipEventRecord(sl.ev_png1, sl.side));
       }
       InfChunk *ich = (InfChunk *)(M + b.ichunk_off);
-      launch_inf_find(sl.st, dd, ich, lst(L_INF_FIND), cnt(L_INF_FIND), inf_stage3_);
-      launch_inf_decode(sl.st, dd, ich, (uint32_t)b.ichunks.size(), inf_decode_);
+      launch_inf_find(sl.st, dd, ich, lst(L_INF_FIND), cnt(L_INF_FIND), opt_.inf_stage3);
+      launch_inf_decode(sl.st, dd, ich, (uint32_t)b.ichunks.size(), opt_.inf_decode);
       launch_inf_resolve(sl.st, dm, ich, lst(L_INF_RES), cnt(L_INF_RES));
       launch_png_inflate(sl.st, dm, lst(L_PNG), cnt(L_PNG), beside ? 1 : 2, fl, ncu_);
       if (beside) HIPCHK(hipStreamWaitEvent(sl.st, sl.ev_png1, 0));
@@ -1860,8 +1433,8 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     if (b.uf_n) {
       uint32_t *uf = (uint32_t *)((char *)sl.scratch.p + b.uf_flags_off);
       HIPCHK(hipMemsetAsync(uf, 0, (size_t)(b.uf_n + 1) * 4, sl.st));
-      launch_png_unfilter(sl.st, dm, lst(L_UNF), cnt(L_UNF), uf, ncu_, b.uf_maxbpp, (uint32_t)(debug_flags_ >> 18) & 1u,
-                          uf_units_, (uint32_t)uf_per_cu_);
+      launch_png_unfilter(sl.st, dm, lst(L_UNF), cnt(L_UNF), uf, ncu_, b.uf_maxbpp, (uint32_t)(opt_.debug_flags >> 18) & 1u,
+                          opt_.uf_units, (uint32_t)opt_.uf_per_cu);
     }
     launch_png_expand(sl.st, dd, lst(L_EXPAND), cnt(L_EXPAND));
     launch_png_expand16(sl.st, dd, lst(L_EXPAND16), cnt(L_EXPAND16));
@@ -1870,7 +1443,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   if (!from_fix) {
     // Lanczos coefficient tables depend only on the plan: compute them on a
     // side stream, overlapped with the entropy decode.
-    hipStream_t cs = side_stream_ ? sl.side : sl.st;
+    hipStream_t cs = opt_.side_stream ? sl.side : sl.st;
     HIPCHK(hipEventRecord(sl.ev_meta, sl.st));
     HIPCHK(hipStreamWaitEvent(cs, sl.ev_meta, 0));
 
@@ -1891,22 +1464,22 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   // level).  On the side stream, beside the baseline images' entropy decode
   // (the main stream waits for it before the IDCT), except with stage timing
   // on, where every stage runs on the main stream so its events bracket it.
-  const bool pside = side_stream_ && prog_side_ && !timing_ && !b.pscans.empty();
+  const bool pside = opt_.side_stream && opt_.prog_side && !opt_.timing && !b.pscans.empty();
   bool dc_side = false;  // DC items on the side stream, AC items on the main one
   if (!from_fix && !b.pscans.empty()) {
     hipStream_t pst = pside ? sl.side : sl.st;
     launch_prog_zero(pst, dd, lst(L_PROG_ZERO), cnt(L_PROG_ZERO));
     const ProgScan *ps = (const ProgScan *)(M + b.pscan_off);
-    const uint32_t prog_dbg = ((uint32_t)(debug_flags_ >> 19) & 1u) << 1;  // forced wait timeouts (tests)
+    const uint32_t prog_dbg = ((uint32_t)(opt_.debug_flags >> 19) & 1u) << 1;  // forced wait timeouts (tests)
     uint64_t *pt = b.ptime_off ? (uint64_t *)((char *)sl.wgt.p + b.ptime_off) : nullptr;
-    if (prog_pipe_) {
+    if (opt_.prog_pipe) {
       // AC items (one Huffman table in LDS) and DC items (four) in launches of
       // their own; no scan of one waits on a scan of the other
       uint32_t *pf = (uint32_t *)((char *)sl.scratch.p + b.pf_off);
       HIPCHK(hipMemsetAsync(pf, 0, (size_t)(b.pf_n + 2) * 4, pst));
-      const uint32_t nac = cnt(L_PROG) - b.prog_dc_n, sflags = (prog_serial_ ? 1u : 0u) | prog_dbg;
+      const uint32_t nac = cnt(L_PROG) - b.prog_dc_n, sflags = (opt_.prog_serial ? 1u : 0u) | prog_dbg;
       hipStream_t dst = pst;
-      if (!pside && side_stream_ && b.prog_dc_n && nac) {  // DC items beside the AC launch (also when timing:
+      if (!pside && opt_.side_stream && b.prog_dc_n && nac) {  // DC items beside the AC launch (also when timing:
                                                           // the IDCT stage then holds what the DC items outlast)
         HIPCHK(hipEventRecord(sl.ev_zero, pst));
         HIPCHK(hipStreamWaitEvent(sl.side, sl.ev_zero, 0));
@@ -1919,7 +1492,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     } else {
       uint32_t at = 0;
       for (uint32_t nl : b.prog_level_n) {
-        launch_prog_scan(pst, dd, ps, lst(L_PROG) + at, nl, hp, prog_serial_ ? 1u : 0u, nullptr, nullptr, pt, 4);
+        launch_prog_scan(pst, dd, ps, lst(L_PROG) + at, nl, hp, opt_.prog_serial ? 1u : 0u, nullptr, nullptr, pt, 4);
         at += nl;
       }
     }
@@ -1929,7 +1502,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   Ckpt *ck = (Ckpt *)((char *)sl.scratch.p + sl.ckpt_off);
   if (!from_fix)
     launch_huff_sync(sl.st, dd, lst(L_SYNC), cnt(L_SYNC), hp, subs, ck, fl, b.stage_on, b.max_slots,
-                     multi_lead_ ? b.max_ac : 0u, sync_pair_, sync2_, (uint32_t)sync_chain_, b.nc4);
+                     opt_.multi_lead ? b.max_ac : 0u, opt_.sync_pair, opt_.sync2, (uint32_t)opt_.sync_chain, b.nc4);
   if (next()) return DG_ERR_DEVICE;
   launch_huff_fix(sl.st, dd, lst(L_SYNC), cnt(L_SYNC), hp, subs, ck, fl, b.stage_on, b.max_slots, b.nc4);
   if (next()) return DG_ERR_DEVICE;
@@ -1941,13 +1514,13 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   if (b.stage_on)
     launch_huff_scatter(sl.st, dd, lst(L_HUFF), cnt(L_HUFF), subs);
   else
-    launch_huff_write(sl.st, dm, lst(L_HUFF), cnt(L_HUFF), hp, subs, fl, b.max_slots, qp, (uint32_t)write_pair_, ck,
+    launch_huff_write(sl.st, dm, lst(L_HUFF), cnt(L_HUFF), hp, subs, fl, b.max_slots, qp, (uint32_t)opt_.write_pair, ck,
                       b.nc4, b.ms);
   if (next()) return DG_ERR_DEVICE;
   if (next()) return DG_ERR_DEVICE;  // coeffs (side stream)
   if (pside || dc_side) HIPCHK(hipStreamWaitEvent(sl.st, sl.ev_prog, 0));  // progressive coefficients
   if (b.any_fused) launch_idct_list(sl.st, dd, qp, fl, std::min<uint32_t>(2048u, (b.idct_cap + 31) / 32));
-  if (idct_thread_)
+  if (opt_.idct_thread)
     launch_idct_t(sl.st, dd, lst(L_IDCT), cnt(L_IDCT), qp);
   else
     launch_idct(sl.st, dd, lst(L_IDCT), cnt(L_IDCT), qp);
@@ -1957,23 +1530,23 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   if (next()) return DG_ERR_DEVICE;
   HIPCHK(hipStreamWaitEvent(sl.st, sl.ev_coef, 0));
   launch_alpha(sl.st, dd, lst(L_ALPHA0), cnt(L_ALPHA0), 0 | (alpha_flags << 8));
-  launch_band_dec(sl.st, dd, lst(L_DEC), b.decclass, qp, dec_strips_ | (dec_dbg_ << 16));
+  launch_band_dec(sl.st, dd, lst(L_DEC), b.decclass, qp, opt_.dec_strips | (opt_.dec_dbg << 16));
   launch_resize_hm(sl.st, dd, lst(L_RM0), b.hmclass[0], 0);
-  launch_resize_hb(sl.st, dd, lst(L_RH0), b.hclass[0], 0, h_prefetch_, h_planar_, b.h_zune != 0);
+  launch_resize_hb(sl.st, dd, lst(L_RH0), b.hclass[0], 0, opt_.h_prefetch, opt_.h_planar, b.h_zune != 0);
   launch_resize_hv(sl.st, dd, lst(L_RHV), b.hvclass);
-  launch_resize_h(sl.st, dd, lst(L_RHX0), cnt(L_RHX0), 0 | ((debug_flags_ & 0xFF) << 8));
+  launch_resize_h(sl.st, dd, lst(L_RHX0), cnt(L_RHX0), 0 | ((opt_.debug_flags & 0xFF) << 8));
   if (!from_fix) launch_r16_v(sl.st, dd, lst(L_R16V), cnt(L_R16V));  // (PNG only: nothing a resync round redoes)
   if (next()) return DG_ERR_DEVICE;
-  launch_resize_v(sl.st, dd, lst(L_RV1), cnt(L_RV1), 1, v_units_);
+  launch_resize_v(sl.st, dd, lst(L_RV1), cnt(L_RV1), 1, opt_.v_units);
   launch_resize_vt(sl.st, dd, lst(L_RVT1), cnt(L_RVT1), 1, b.v_tile);
   if (!from_fix) launch_r16_h(sl.st, dd, lst(L_R16H), cnt(L_R16H));
   launch_alpha(sl.st, dd, lst(L_ALPHA1), cnt(L_ALPHA1), 1 | (alpha_flags << 8));
   if (next()) return DG_ERR_DEVICE;
   launch_resize_hm(sl.st, dd, lst(L_RM2), b.hmclass[1], 2);
-  launch_resize_hb(sl.st, dd, lst(L_RH2), b.hclass[1], 2, h_prefetch_, h_planar_, b.h_zune != 0);
-  launch_resize_h(sl.st, dd, lst(L_RHX2), cnt(L_RHX2), 2 | ((debug_flags_ & 0xFF) << 8));
+  launch_resize_hb(sl.st, dd, lst(L_RH2), b.hclass[1], 2, opt_.h_prefetch, opt_.h_planar, b.h_zune != 0);
+  launch_resize_h(sl.st, dd, lst(L_RHX2), cnt(L_RHX2), 2 | ((opt_.debug_flags & 0xFF) << 8));
   if (next()) return DG_ERR_DEVICE;
-  launch_resize_v(sl.st, dd, lst(L_RV3), cnt(L_RV3), 3, v_units_);
+  launch_resize_v(sl.st, dd, lst(L_RV3), cnt(L_RV3), 3, opt_.v_units);
   launch_resize_vt(sl.st, dd, lst(L_RVT3), cnt(L_RVT3), 3, b.v_tile);
   launch_alpha(sl.st, dd, lst(L_ALPHA2), cnt(L_ALPHA2), 2 | (alpha_flags << 8));
   if (next()) return DG_ERR_DEVICE;
@@ -2152,7 +1725,7 @@ dg_status Context::finish_body(Slot &sl) {
       wgstat_[a][3] = d.back();
     }
   }
-  if (timing_) {
+  if (opt_.timing) {
     last_ms_.assign(kNumStages, 0.f);
     for (int i = 0; i < kNumStages; i++) {
       float ms = 0.f;
@@ -2246,7 +1819,7 @@ dg_status Context::finish_body(Slot &sl) {
       off += align_up(b.plans[i].out_bytes, 16);
     }
   }
-  parallel_copy(copies, copy_threads_);
+  parallel_copy(copies, opt_.copy_threads);
   for (size_t i = 0; i < b.pub.size(); i++) *b.pub[i] = b.local_meta[i];  // defer_meta: publish now
   b.done = true;
   return DG_OK;
@@ -2315,7 +1888,7 @@ dg_status Context::flush_batch(std::vector<OneReq *> &batch, bool prog) {
 dg_status Context::decode_one(const uint8_t *src, size_t len, int32_t forced, uint8_t *out, uint64_t cap,
                               dg_payload_meta *meta) {
   OneReq r{src, len, forced, out, cap, meta, false, DG_OK, false};
-  if (coalesce_max_ <= 1) {
+  if (opt_.coalesce_max <= 1) {
     std::vector<OneReq *> one{&r};
     flush_batch(one, false);
     return r.st;
@@ -2324,25 +1897,25 @@ dg_status Context::decode_one(const uint8_t *src, size_t len, int32_t forced, ui
   // for a large file), so they coalesce into batches of their own: a
   // baseline caller never waits behind a progressive chain, and up to
   // prog_lanes progressive batches run beside the baseline ones.
-  r.prog = progressive_ && prog_lanes_ > 0 && jpeg_sniff_progressive(src, len);
+  r.prog = opt_.progressive && opt_.prog_lanes > 0 && jpeg_sniff_progressive(src, len);
   std::unique_lock<std::mutex> lk(cmu_);
   callers_++;
   std::vector<OneReq *> &q = r.prog ? ppending_ : pending_;
   q.push_back(&r);
-  const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(coalesce_us_);
+  const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(opt_.coalesce_us);
   for (;;) {
     if (r.done) break;
     // flush when the batch is full, when every caller in here is already
     // waiting (nobody else can add), or at the deadline; nslots baseline
     // batches (+ prog_lanes progressive ones) in flight at most
     const int waiting = callers_ - inflight_reqs_;
-    const bool ready = !q.empty() && ((int)q.size() >= coalesce_max_ ||
+    const bool ready = !q.empty() && ((int)q.size() >= opt_.coalesce_max ||
                                       (int)(pending_.size() + ppending_.size()) >= waiting ||
                                       std::chrono::steady_clock::now() >= deadline);
-    const bool room = r.prog ? pinflight_ < prog_lanes_ : inflight_ < (coalesce_inflight_ ? coalesce_inflight_ : nslots_);
+    const bool room = r.prog ? pinflight_ < opt_.prog_lanes : inflight_ < (opt_.coalesce_inflight ? opt_.coalesce_inflight : opt_.nslots);
     if (ready && room && std::find(q.begin(), q.end(), &r) != q.end()) {
       std::vector<OneReq *> batch;
-      const size_t take = std::min(q.size(), (size_t)coalesce_max_);
+      const size_t take = std::min(q.size(), (size_t)opt_.coalesce_max);
       batch.assign(q.begin(), q.begin() + take);
       q.erase(q.begin(), q.begin() + take);
       (r.prog ? pinflight_ : inflight_)++;
@@ -2397,7 +1970,7 @@ dg_status Context::poll(uint64_t ticket) {
 // older than prog_flush_us AND a progressive slot is idle: while both run,
 // the aggregate keeps growing (a larger launch hides more of its long pole).
 bool Context::pagg_stale_locked() {
-  if (pagg_.empty() || std::chrono::steady_clock::now() - pagg_t0_ < std::chrono::microseconds(prog_flush_us_))
+  if (pagg_.empty() || std::chrono::steady_clock::now() - pagg_t0_ < std::chrono::microseconds(opt_.prog_flush_us))
     return false;
   std::lock_guard<std::mutex> lk(mu_);
   for (int j = 0; j < kProgSlots; j++) {
@@ -2439,7 +2012,7 @@ dg_status Context::submit_split(int n, const uint8_t *const *h_srcs, const uint8
   const int h = n / 2;
   st = submit_split(h, h_srcs, d_srcs, lens, forced, outs, caps, mptrs, host_io, tickets, prog, defer_meta);
   if (st) return st;
-  if (debug_flags_ & (1 << 24)) {  // test switch: the second part fails after the first launched
+  if (opt_.debug_flags & (1 << 24)) {  // test switch: the second part fails after the first launched
     set_error("forced failure of a split submission's second part (debug_flags bit 24)");
     return DG_ERR_DEVICE;
   }
@@ -2499,7 +2072,7 @@ dg_status Context::submit_user(int n, const uint8_t *const *h_srcs, const uint8_
   if (!ticket) return DG_ERR_INVALID;
   std::vector<uint8_t> isp(n > 0 ? n : 0, 0);
   int np = 0;
-  if (progressive_ && prog_split_ && n > 0 && h_srcs && lens && outs && caps && metas && (host_io || d_srcs))
+  if (opt_.progressive && opt_.prog_split && n > 0 && h_srcs && lens && outs && caps && metas && (host_io || d_srcs))
     for (int i = 0; i < n; i++) {
       isp[i] = h_srcs[i] && jpeg_sniff_progressive(h_srcs[i], lens[i]) ? 1 : 0;
       np += isp[i];
@@ -2580,7 +2153,7 @@ dg_status Context::submit_user(int n, const uint8_t *const *h_srcs, const uint8_
   // launch started here may carry other submissions' members too: its
   // failure is recorded for their dg_wait (pgen_) and in their metas, never
   // returned from this call, whose non-progressive part is already in flight.
-  if ((int)pagg_.size() >= prog_batch_ || pagg_stale_locked()) flush_pagg_locked();
+  if ((int)pagg_.size() >= opt_.prog_batch || pagg_stale_locked()) flush_pagg_locked();
   return DG_OK;
 }
 

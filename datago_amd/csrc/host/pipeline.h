@@ -14,6 +14,7 @@
 #include "../dg_types.h"
 #include "../dg_resize16.h"
 #include "buckets.h"
+#include "options.h"
 #include "jpeg_header.h"
 #include "gif_header.h"
 #include "webp_header.h"
@@ -158,16 +159,8 @@ struct Batch {
   std::vector<CProd> ccache_prod;
 };
 
-// One in-flight batch's device/pinned buffers.  Three (option "slots", 1 to
-// kMaxInflight) slots let the host plan and upload batch k+1 while the GPU
-// still runs batches k and k-1.  kProgSlots more run progressive batches only
-// (dg_submit's progressive aggregates, dg_decode_one's progressive lanes), so a
-// ~0.1-1 s refinement chain never holds a baseline slot.
-constexpr int kMaxInflight = 6;
-#ifndef DG_PROG_SLOTS
-#define DG_PROG_SLOTS 2
-#endif
-constexpr int kProgSlots = DG_PROG_SLOTS;  // (-DDG_PROG_SLOTS=n: experiment builds)
+// One in-flight batch's device/pinned buffers: kMaxInflight slots for baseline
+// batches, kProgSlots more for progressive ones (options.h).
 constexpr int kAllSlots = kMaxInflight + kProgSlots;
 struct Slot {
   DevBuf scratch, meta, input;
@@ -369,22 +362,17 @@ class Context {
   void ccache_index_clear();
   std::vector<CEntry> ccache_;
   DevBuf d_ccache_;
-  size_t ccache_off_ = 0, ccache_cap_ = (size_t)256 << 20;
+  size_t ccache_off_ = 0;
   bool ccache_full_ = false;  // an entry did not fit: start over at the next submit
   int64_t stat_ccache_hits_ = 0, stat_ccache_new_ = 0, stat_ccache_resets_ = 0;
   int ccache_lookup(const ResizePass &ps, Batch &b, bool &hit);  // mu_ held; -1 = not cached
   void ccache_maybe_reset(Slot &self);                            // mu_ held, before a batch's lookups
   void ccache_clear(bool free_arena);                             // mu_ held, no batch in flight uses the cache
   void ccache_rollback(size_t n0, size_t off0);                   // a submit that installs no batch
-  size_t max_dev_bytes_ = 0;        // option "max_device_mb" (0: no budget)
   size_t budget_room_ = 0;          // headroom the current submit's growth may take under the budget
   int budget_slots_ = kMaxInflight;  // baseline slots in turn under the budget (budget_fit lowers it)
   int64_t stat_budget_slots_min_ = kMaxInflight;
-  // Planned budget (option "budget_plan", default 1): the
-  // first baseline batch under a budget decides the slot count and each
-  // slot's buffer sizes from the budget, and every planned slot is sized
-  // then; later batches that do not fit their slot are split, never grown.
-  bool budget_plan_ = true;
+  // Planned budget (option "budget_plan", Options::budget_plan)
   bool budget_planned_ = false;
   size_t plan_arena_ = 0;  // planned bytes per slot (scratch + coefficients + input, one allocation)
   bool queue_set_ = false;  // slot_queue / side_queue set explicitly (else a budget shares the process queues)
@@ -392,6 +380,7 @@ class Context {
   int64_t stat_peak_dev_ = 0, stat_budget_splits_ = 0, stat_budget_frees_ = 0, stat_budget_oom_ = 0;
   dg_status finish(Slot &sl);       // finish_body, or fail_batch on its error
   dg_status finish_body(Slot &sl);
+  dg_status finish_slots(int first, int count);  // mu_ held: the batches in flight on these slots finish
   void fail_batch(Slot &sl, dg_status st);
   Slot *find(uint64_t ticket);
   int pick_slot();
@@ -424,7 +413,6 @@ class Context {
   std::condition_variable ccv_;
   std::vector<OneReq *> pending_, ppending_;  // baseline / progressive callers waiting for a batch
   int callers_ = 0, inflight_ = 0, inflight_reqs_ = 0, pinflight_ = 0;
-  int prog_lanes_ = 1;  // option "prog_lanes": progressive batches in flight beside the baseline ones
   // progressive aggregate of split submissions (options "prog_split", "prog_batch", "prog_flush_us")
   struct PEntry {
     std::vector<uint8_t> host;  // the coded file (the header parser walks every scan at flush time)
@@ -454,24 +442,8 @@ class Context {
   std::unordered_map<uint64_t, SplitRec> split_;                 // user ticket -> parts
   int pagg_refs_ = 0;      // split records referring to the open aggregate
   int next_pslot_ = 0;
-  bool prog_split_ = true;
-  int prog_batch_ = 2048;
-  int prog_flush_us_ = 20000;
-  int slot_queue_ = 1;      // option "slot_queue" (make_streams for the baseline slots): high priority
-  int side_queue_ = 3;      // option "side_queue": the baseline slots' side streams (-1: as slot_queue; 3: own queues)
-  int prog_cus_ = 0;        // option "prog_cus" (prog_queue 3: CU mask width, 0 = all)
-  int prog_queue_ = 2;      // option "prog_queue" (make_prog_streams): low priority, a queue of its own
+  Options opt_;  // what dg_ctx_set_option sets (options.h)
   int64_t stat_prog_aggs_ = 0, stat_prog_agg_images_ = 0;
-  bool multi_lead_ = true;   // option "multi_lead": multi-symbol AC steps in k_huff_sync's state-only decodes
-  int write_pair_ = 3;       // option "write_pair": up to this many more AC symbols per k_huff_write step from one peek
-  bool sync2_ = false;       // option "sync2": k_huff_sync with two chains per lane (k_huff_sync2)
-  int sync_chain_ = 2;       // option "sync_chain": up to this many more multi entries per k_huff_sync step from one peek
-  bool sync_pair_ = false;   // option "sync_pair": the same in k_huff_sync (measured slower beside multi_lead: off)
-  bool prog_side_ = false;  // option "prog_side": progressive scans on the side stream (measured slower: off)
-  int coalesce_max_ = 64, coalesce_us_ = 500;
-  // option "coalesce_inflight": coalesced batches in flight (0 = nslots_); 3 fills the batches better
-  // (7.6 vs 5.4 images) and measured 5-20% faster than 4 from 32 callers (profiles/r04/one_r4*)
-  int coalesce_inflight_ = 3;
   int64_t stat_coalesced_batches_ = 0, stat_coalesced_images_ = 0;
   dg_status flush_batch(std::vector<OneReq *> &batch, bool prog);
 
@@ -493,79 +465,16 @@ class Context {
 
   Slot slots_[kAllSlots];  // [0, kMaxInflight): baseline batches; then kProgSlots progressive ones
   uint32_t ncu_ = 256;  // compute units: persistent-worker grids
-  int entropy_prio_ = 0;  // option "entropy_prio"
-  int uf_per_cu_ = 0;     // option "uf_per_cu"
-  int nslots_ = 4;  // option "slots": batches in flight (each slot: own streams + scratch; 4 measured +2% over 3 with own queues)
   int next_slot_ = 0;
   uint64_t next_ticket_ = 1;
 
-  uint32_t sub_bits_ = 0;  // 0 = auto per batch (see submit)
-  uint32_t sub_auto_ = 8192;  // the auto size of large batches
-  int64_t lead_bits_ = -1;  // -1 = auto per image (see submit)
   uint32_t last_sub_bits_ = kDefaultSubBits;
-  bool timing_ = false;
-  bool side_stream_ = true;
-  int debug_flags_ = 0;
-  bool wg_timing_ = false;
-  bool chunked_off_ = false;  // option "png_chunked" = 0
-  uint32_t inf_chunk_ = kInfChunk;  // option "inf_chunk"
-  uint32_t inf_cap_ = 30;           // option "inf_cap": chunk entries, tenths of the expansion of a span
-  bool png_alias_ = true;           // option "png_alias": chunk entries alias the unfilter/resize buffers
-  uint32_t inf_pad_ = 65536;        // option "inf_pad": chunk entries on top of inf_cap's
-  uint32_t inf_stage3_ = 32;        // option "inf_stage3"
-  int plan_threads_ = 4;            // option "plan_threads"
-  int meta_pull_ = 1;               // option "meta_pull"
   size_t list_hint_[L_COUNT] = {};  // work-list sizes of the previous batch (reserve)
-  bool write_split_ = true;         // option "write_split"
-  uint32_t lead_big_ = 4096;        // option "lead_big" (6144 -> 4096 with 8192-bit ranges: +1.3%, profiles/r04/lead_big)
-  uint64_t small_coded_ = 0;        // option "small_coded" (0: off)
-  uint32_t sub_small_ = 512, lead_small_ = 1024;  // options "sub_small", "lead_small"
-  uint32_t v_tile_ = 4;             // option "v_tile": V pass on R-row column tiles (k_resize_vt<R>; 0 = k_resize_v)
-  uint32_t v_units_ = 2;            // option "v_units" (profiles/r04/v_units: 1 / 2 / 4 -> V traffic 1.95 / ? / 3.91 GB per batch)
   static constexpr int kPlanGrain = 32;  // images per planning work piece
   std::unique_ptr<HostPool> plan_pool_;
-  uint32_t hb_bands_ = kHBandsDefault;  // option "hb_bands"
-  int decode_sem_ = 0;                  // option "decode_semantics"
-  bool ckpt_ = true;                    // option "ckpt"
   double host_us_[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // submit phases + slot wait (stats "host_us_*"; option "reset_host_us")
   double host_cpu_us_[7] = {0, 0, 0, 0, 0, 0, 0};
   size_t last_meta_bytes_ = 0;  // stat "meta_bytes": the last batch's descriptor/list upload  // the same phases' thread CPU time (stats "host_cpu_us_*")
-  int copy_threads_ = 8;                // option "copy_threads": host threads for a host-out batch's output copies
-  bool hv_fused_ = false;               // option "hv_fused": first H + V pass fused (k_resize_hv) when it fits
-  bool idct_thread_ = true;             // option "idct_thread": one lane per block (k_idct_t) instead of 8 (k_idct)
-  bool sparse_coef_ = true;             // option "sparse_coef": k_huff_write stores, k_idct_t loads, only the
-                                        // 16-byte parts through each block's last nonzero (ImageDesc::ccnt)
-  bool h_prefetch_ = true;              // option "h_prefetch": specialised fused fills load the next band before the convolution
-  bool h_planar_ = true;                // option "h_planar": fused 8/16-tap band passes over planar u16-pair segments (k_resize_hbp)
-  bool destuff_one_ = false;            // option "destuff_one": single-pass destuff with decoupled look-back
-                                        // (configs[1] 0.66 vs 0.43 ms three-pass: off)
-  bool chroma_rec_ = true;              // option "chroma_rec": half-rate chroma planes as 8-byte records (dg_plane.h)
-  bool band_dec_ = false;               // option "band_dec": IDCT + colour + first H pass in k_band_dec
-  uint32_t uf_units_ = 1;               // option "uf_units": PNG unfilter units per lane per step (1 or 2; round 5: 1)
-  uint32_t inf_decode_ = 25;            // option "inf_decode": k_inf_decode shape (25 = 7/5 lookup bits, 20 KiB LDS
-                                        // per wave, 16 stream words per lane in registers)
-  bool h_mfma_ = false;                 // option "h_mfma": band H passes on the matrix cores (k_resize_hm; measured slower: off)
-  double sub_density_ = 0;              // option "sub_density": bits per block below which subsequences shrink
-  bool lead_density_ = false;           // option "lead_density": their lead-in shrinks by the same factor
-  uint32_t dec_dbg_ = 0;                // option "dec_dbg": k_band_dec phase switches (timing experiments only)
-  uint32_t dec_strips_ = kDecStripsDefault;  // option "dec_strips"
-  bool idct_fused_ = false;             // option "idct_fused" (measured 7x slower k_huff_write: off)
-  bool progressive_ = true;             // option "progressive"
-  bool png16_ = false;                  // option "png16": 16-bit PNGs decode on the GPU
-  bool gif_ = false;                    // option "gif": a GIF's first frame decodes on the GPU (dg_gif.hip)
-  bool webp_ = false;                   // option "webp": a lossless WebP decodes on the GPU (dg_vp8l.hip)
-  bool jpeg_h1v2_ = false;              // option "jpeg_h1v2": 4:4:0-style JPEGs decode on the GPU
-  bool jpeg_cmyk_ = false;              // option "jpeg_cmyk": Adobe CMYK / YCCK JPEGs decode on the GPU (to RGB)
-  bool jpeg_multiscan_ = false;         // option "jpeg_multiscan": non-interleaved baseline JPEGs decode on the GPU
-  bool resize16_ = false;               // option "resize16": ... and resize to their bucket (dg_resize16.hip)
-  bool penc16_ = false;                 // option "penc16": ... and go into the PNG re-encoder as 16-bit samples (dg_penc16.h)
-  bool penc_dynamic_ = false;           // option "penc_dynamic": PNG re-encode with per-image Huffman codes where shorter
-  bool jenc_optimize_ = false;          // option "jenc_optimize": JPEG re-encode with per-image Huffman tables
-  bool prog_serial_ = false;            // option "prog_serial": serial reader for every scan (A/B)
-  bool prog_pipe_ = true;               // option "prog_pipe": all scans in one pipelined launch (0: one launch per level)
-  int prog_chain_ = 100;                // option "prog_chain": chain dependency groups costing <= this % of the longest scan
-  bool entropy_lpt_ = true;             // option "entropy_lpt": slow entropy workgroups first
-  bool entropy_once_ = false;           // option "entropy_once": decode-once staging + k_huff_scatter
   int64_t stat_png_serial_ = 0, stat_png_chunks_ = 0, stat_png_small_ = 0;
   int64_t stat_band_dec_ = 0;  // images whose first H pass ran in k_band_dec (stat "band_dec_images")
   // "wg_timing" summaries of the last batch (microseconds): per kernel {span, mean, p90, max}

@@ -266,7 +266,7 @@ dg_status Context::submit(int n, const uint8_t *const *h_srcs, const uint8_t *co
   phase(6);
   stat_batches_++;
   *ticket = sl.batch->ticket;
-  if ((!max_dev_bytes_ || budget_planned_) && stat_batches_ <= 2 * kMaxInflight) prewarm_slots(sl);
+  if ((!opt_.max_dev_bytes || budget_planned_) && stat_batches_ <= 2 * kMaxInflight) prewarm_slots(sl);
   return DG_OK;
 }
 
@@ -331,8 +331,8 @@ void Context::plan_images(const SubmitArgs &a, Batch &b) {
       m.status = DG_ERR_INVALID;
     }
   };
-  if (plan_threads_ > 1 && a.n >= 2 * kPlanGrain) {
-    if (!plan_pool_ || plan_pool_->threads() != plan_threads_) plan_pool_.reset(new HostPool(plan_threads_));
+  if (opt_.plan_threads > 1 && a.n >= 2 * kPlanGrain) {
+    if (!plan_pool_ || plan_pool_->threads() != opt_.plan_threads) plan_pool_.reset(new HostPool(opt_.plan_threads));
     plan_pool_->run(a.n, kPlanGrain, plan_one);
   } else {
     for (int i = 0; i < a.n; i++) plan_one(i);
@@ -405,22 +405,22 @@ dg_status Context::pool_tables(Batch &b) {
 // decode_one trace, profiles/r04/one_trace), so they take short ranges and
 // lead-ins ("sub_small", "lead_small") at the cost of more total decode.
 void Context::choose_sub_bits(const Batch &b, BatchLayout &bl) {
-  bl.sub_bits = sub_bits_;
+  bl.sub_bits = opt_.sub_bits;
   bl.small = false;
   if (!bl.sub_bits) {
     uint64_t coded = 0;
     for (int i = 0; i < b.n; i++)
       if (!b.plans[i].status && b.plans[i].fmt == kFmtJpeg && !b.plans[i].hdr.progressive)
         coded += b.plans[i].hdr.scan_end - b.plans[i].hdr.scan_off;
-    bl.small = coded < small_coded_;
-    bl.sub_bits = coded >= (64ull << 20) ? sub_auto_ : bl.small ? sub_small_ : 2048u;
+    bl.small = coded < opt_.small_coded;
+    bl.sub_bits = coded >= (64ull << 20) ? opt_.sub_auto : bl.small ? opt_.sub_small : 2048u;
   }
   last_sub_bits_ = bl.sub_bits;
 }
 
 // first pass: sizes only (pointers are patched after allocation)
 void Context::layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl) {
-  bl.alias = png_alias_;
+  bl.alias = opt_.png_alias;
   bl.in_off.assign(a.n, 0);
   b.out_dev_off.assign(a.n, 0);
   b.out_direct.assign(a.n, 0);
@@ -482,7 +482,7 @@ void Context::layout_scan(int i, int j, Batch &b, BatchLayout &bl) {
   d.sample_bytes = 1;
   d.ncomp = (uint8_t)sc.ns;
   d.sem = par.sem;
-  d.ckpt = ckpt_ ? 1u : 0u;
+  d.ckpt = opt_.ckpt ? 1u : 0u;
   d.ms = ms_scan_map(par, (uint32_t)sc.ns, sc.comp, d.total_blocks);
   uint32_t bpm = 0;
   for (int q = 0; q < sc.ns; q++) {  // the scan's components, numbered in scan order
@@ -552,9 +552,9 @@ void Context::layout_png(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, 
   // e.g. masks, inflate serially in one wave)
   {
     const uint64_t want = g.rawlen;
-    const uint32_t span = inf_chunk_;
+    const uint32_t span = opt_.inf_chunk;
     const uint32_t nch = (uint32_t)((g.zlen + span - 1) / span);
-    if (nch >= 2 && !chunked_off_) {
+    if (nch >= 2 && !opt_.chunked_off) {
       pd.chunk0 = (uint32_t)b.ichunks.size();
       pd.nchunks = nch;
       // entries per chunk: inf_cap / 10 times the image's average expansion of a span (+64 Ki), at
@@ -562,7 +562,7 @@ void Context::layout_png(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, 
       // entries (2 bytes per output byte) are most of a PNG batch's device memory: 3x made them
       // 6x the raw image
       const double ratio = (double)want / (double)g.zlen;
-      const uint64_t cap = std::min<uint64_t>(want, (uint64_t)(0.1 * inf_cap_ * ratio * span) + inf_pad_);
+      const uint64_t cap = std::min<uint64_t>(want, (uint64_t)(0.1 * opt_.inf_cap * ratio * span) + opt_.inf_pad);
       for (uint32_t k = 0; k < nch; k++) {
         InfChunk c;
         memset(&c, 0, sizeof(c));
@@ -657,8 +657,8 @@ void Context::layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl,
   d.height = H;
   d.ncomp = (uint8_t)h.ncomp;
   d.colorspace = (uint8_t)h.colorspace;
-  d.sem = (uint16_t)decode_sem_;
-  d.ckpt = ckpt_ ? 1u : 0u;
+  d.sem = (uint16_t)opt_.decode_sem;
+  d.ckpt = opt_.ckpt ? 1u : 0u;
   d.dec_c = h.ncomp == 1 ? 1 : 3;
   d.hmax = (uint32_t)h.hmax;
   d.vmax = (uint32_t)h.vmax;
@@ -729,7 +729,7 @@ void Context::layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl,
   // sparse blocks: k_huff_write's cooperative flush + k_idct_t only (not the
   // fused / decode-once writers, k_idct or k_band_dec; progressive scans
   // write whole blocks)
-  o.ccnt = (sparse_coef_ && idct_thread_ && !d.prog && !d.idct_fused && !(entropy_once_ && !b.nc4 && !b.ms))
+  o.ccnt = (opt_.sparse_coef && opt_.idct_thread && !d.prog && !d.idct_fused && !(opt_.entropy_once && !b.nc4 && !b.ms))
                ? bl.CO.take((size_t)d.total_blocks, 64) + 1
                : 0;
   for (int c = 0; c < 4; c++) o.plane[c] = (size_t)-1;  // allocated after the pass plan (not for k_band_dec)
@@ -748,7 +748,7 @@ void Context::layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &
 void Context::layout_entropy_stream(size_t scan_len, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
   const uint32_t sub_bits = bl.sub_bits;
   // (a batch with a four-component or a multiscan image: the default write pass)
-  const bool once = entropy_once_ && !b.nc4 && !b.ms;
+  const bool once = opt_.entropy_once && !b.nc4 && !b.ms;
   d.scan_len = (uint32_t)scan_len;
   // Per-image subsequence size (option "sub_density" T > 0): a lane's
   // decode time follows its symbols and blocks, not its bits, so images
@@ -757,20 +757,20 @@ void Context::layout_entropy_stream(size_t scan_len, Batch &b, BatchLayout &bl, 
   // bits per block, a quarter below T / 2 -- and their workgroups stop
   // forming the entropy kernels' tail.
   d.sub_bits = sub_bits;
-  if (sub_density_ > 0 && sub_bits_ == 0) {
+  if (opt_.sub_density > 0 && opt_.sub_bits == 0) {
     const double bpb = (double)d.scan_len * 8.0 / (double)std::max<uint32_t>(1, d.total_blocks);
-    if (bpb < sub_density_ * 0.5 && sub_bits >= 2048)
+    if (bpb < opt_.sub_density * 0.5 && sub_bits >= 2048)
       d.sub_bits = sub_bits / 4;
-    else if (bpb < sub_density_ && sub_bits >= 1024)
+    else if (bpb < opt_.sub_density && sub_bits >= 1024)
       d.sub_bits = sub_bits / 2;
   }
   // completed blocks go straight to plane pixels inside k_huff_write (not
   // with decode-once staging, whose k_huff_scatter writes coefficients)
-  d.idct_fused = (idct_fused_ && !once && !b.nc4 && !b.ms) ? 1u : 0u;
+  d.idct_fused = (opt_.idct_fused && !once && !b.nc4 && !b.ms) ? 1u : 0u;
   // k_huff_write splits each range at the sync pass's half-way checkpoint
   // (option "write_split"): needs that checkpoint, no restart markers and
   // the plain write path
-  if (write_split_ && d.ckpt && !d.idct_fused && !once && d.restart == 0 && d.sub_bits >= 1024 &&
+  if (opt_.write_split && d.ckpt && !d.idct_fused && !once && d.restart == 0 && d.sub_bits >= 1024 &&
       d.sub_bits / 2 / kCkptBits - 1 < num_ckpt(d.sub_bits))
     d.ckpt |= 2u;
   if (d.idct_fused) b.any_fused = true;
@@ -780,10 +780,10 @@ void Context::layout_entropy_stream(size_t scan_len, Batch &b, BatchLayout &bl, 
   // Option "lead_big" (4096): shorter than that tail, but a wrong entry
   // guess only costs a re-decode up to the first checkpoint where it merges
   // (6144 -> 4096: +1.3% on configs[1]; 2048 / 1024 slower on configs[2])
-  d.lead_bits = lead_bits_ >= 0 ? (uint32_t)lead_bits_ : bl.small ? lead_small_ : (d.bpm >= 4 ? lead_big_ : 2048u);
+  d.lead_bits = opt_.lead_bits >= 0 ? (uint32_t)opt_.lead_bits : bl.small ? opt_.lead_small : (d.bpm >= 4 ? opt_.lead_big : 2048u);
   // shorter ranges of symbol-dense images get a proportionally shorter lead-in (option
   // "lead_density"): their codes are short, so the decoder self-synchronises in fewer bits
-  if (lead_density_ && lead_bits_ < 0 && d.sub_bits < sub_bits)
+  if (opt_.lead_density && opt_.lead_bits < 0 && d.sub_bits < sub_bits)
     d.lead_bits = std::max<uint32_t>(1024u, d.lead_bits / (sub_bits / d.sub_bits));
   d.nsub = std::max<uint32_t>(1, (uint32_t)(((uint64_t)d.scan_len * 8 + d.sub_bits - 1) / d.sub_bits));
   d.sub_base = bl.sub_base;
@@ -841,7 +841,7 @@ int Context::plan_resize(const ImagePlan &p, Batch &b, BatchLayout &bl, ImageDes
     ps.width = width;
     ps.rows = rows;
     ps.row0 = row0;
-    ps.bands = hb_bands_;
+    ps.bands = opt_.hb_bands;
     ps.C = C;
     ps.dst_stride = (uint32_t)align_up((size_t)width * C, 16);
     o.pass_srcoff[stage] = (size_t)xoff * C;  // column window of the source (V passes)
@@ -933,16 +933,16 @@ int Context::plan_resize(const ImagePlan &p, Batch &b, BatchLayout &bl, ImageDes
   }
   // colour images whose first pass is not a fused H pass need the RGB image
   d.color_fused = colour && d.pass[0].kind == 1 && (d.pass[0].mode & kHFused);
-  if (hv_fused_ && hv_fusable(d.pass[0], d.pass[1])) d.pass[0].mode |= kHVFused;
+  if (opt_.hv_fused && hv_fusable(d.pass[0], d.pass[1])) d.pass[0].mode |= kHVFused;
   if (p.fmt == kFmtJpeg) {
     // k_band_dec decodes pass[0]'s source from the coefficients: no planes
-    const uint32_t dm = band_dec_ ? band_dec_mode(d, d.pass[0]) : 0u;
+    const uint32_t dm = opt_.band_dec ? band_dec_mode(d, d.pass[0]) : 0u;
     d.pass[0].mode |= dm;
     if (dm) stat_band_dec_++;
     if (!dm)
       for (uint32_t c = 0; c < d.ncomp; c++) {
         // half-rate chroma as 8-byte records (dg_plane.h, option "chroma_rec"): twice the bytes
-        const bool rec = chroma_rec_ && d.ncomp == 3 && d.hmax == 2 * d.ch[c];
+        const bool rec = opt_.chroma_rec && d.ncomp == 3 && d.hmax == 2 * d.ch[c];
         if (rec) d.crec |= 1u << c;
         o.plane[c] = bl.L.take((size_t)d.cbw[c] * 8 * d.cbh[c] * 8 * (rec ? 2 : 1));
       }
@@ -1068,9 +1068,9 @@ void Context::layout_output_and_encode(const SubmitArgs &a, int i, int last_stag
     e.dyn = 0;
     // option "penc_dynamic": the image's histogram / code table (dg_penc_tree.h) in front of its bit buffer,
     // inside the region the batch zeroes
-    o.etab = penc_dynamic_ ? kPencTabBytes : 0;
+    o.etab = opt_.penc_dynamic ? kPencTabBytes : 0;
     o.ewords += o.etab;
-    b.penc_dyn = b.penc_dyn || penc_dynamic_;
+    b.penc_dyn = b.penc_dyn || opt_.penc_dynamic;
     b.any_enc = true;
   } else if (p.encode) {  // the transform lands in tout; the JPEG goes to the caller's buffer
     EncDesc &e = d.enc;
@@ -1102,9 +1102,9 @@ void Context::layout_output_and_encode(const SubmitArgs &a, int i, int last_stag
     o.ewords = (size_t)(e.nblocks * 210ull + 64) / 4 * 4 + 16;  // size for now; placed with the batch's regions
     // option "jenc_optimize": the image's histogram, EncTables and DHT segments (dg_jenc_tree.h) in front of its
     // bit buffer, inside the region the batch zeroes
-    o.etab = jenc_optimize_ ? kJencOptBytes : 0;
+    o.etab = opt_.jenc_optimize ? kJencOptBytes : 0;
     o.ewords += o.etab;
-    b.jenc_opt = b.jenc_opt || jenc_optimize_;
+    b.jenc_opt = b.jenc_opt || opt_.jenc_optimize;
     b.any_enc = true;
   }
 }
@@ -1167,7 +1167,7 @@ void Context::layout_batch_regions(Batch &b, BatchLayout &bl) {
   b.ds_n = 0;
   for (const ImageDesc &dd : b.descs)
     if (dd.fmt == kFmtJpeg && !dd.prog) b.ds_n += dd.nchunk;
-  b.ds_state_off = (destuff_one_ && b.ds_n) ? L.take((size_t)(b.ds_n + 1) * 8) : 0;
+  b.ds_state_off = (opt_.destuff_one && b.ds_n) ? L.take((size_t)(b.ds_n + 1) * 8) : 0;
   bl.subs_off = L.take(b.total_subs * sizeof(SubState));
   bl.ckpt_off = L.take(std::max<uint64_t>(1, bl.ckpt_total) * (b.nc4 ? sizeof(CkptN<4>) : sizeof(Ckpt)));
   // fused IDCT leftovers: at most one carried-in block per subsequence, plus
@@ -1189,7 +1189,7 @@ void Context::layout_batch_regions(Batch &b, BatchLayout &bl) {
 // finishes the other slots' batches and frees their buffers, then splits.
 dg_status Context::fit_device(Slot &sl, const Batch &b, const BatchLayout &bl) {
   const size_t rs = bl.L.off + 256, rc = bl.CO.off + 256, ri = b.host_io ? bl.IN.off + 64 : 0;
-  const bool planned = max_dev_bytes_ && budget_plan_ && &sl - slots_ < kMaxInflight;
+  const bool planned = opt_.max_dev_bytes && opt_.budget_plan && &sl - slots_ < kMaxInflight;
   dg_status st = DG_OK;
   if (planned) {
     st = budget_planned_fit(sl, rs, rc, ri);
@@ -1438,7 +1438,7 @@ void Context::build_lists(Batch &b) {
   ClassLists cl;
   for (int di = 0; di < (int)b.descs.size(); di++) image_items(di, b, cl);
   for (int l = 0; l < L_COUNT; l++) list_hint_[l] = b.lists[l].size();
-  if (entropy_lpt_) {
+  if (opt_.entropy_lpt) {
     // Entropy workgroups decode a fixed number of bits, but their time follows
     // the symbol count: images with few coded bits per block (low quality,
     // flat content: short EOB-heavy codes) run up to 2x the mean.  Dispatch
@@ -1488,7 +1488,7 @@ void Context::build_lists(Batch &b) {
     b.prog_level_n[lv]++;
   }
   b.prog_dc_n = 0;
-  if (prog_pipe_) {
+  if (opt_.prog_pipe) {
     plan_prog_items(b);
   } else {  // one launch per level: scans grouped by level
     std::vector<uint32_t> at(b.prog_level_n.size(), 0);
@@ -1572,7 +1572,7 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
     uint32_t items = 0;
     for (uint32_t c = 0; c < d.ncomp; c++) items += d.cbh[c] * ((d.cbw[c] + 63) / 64);  // kIdctBlocks
     if (!d.idct_fused && !(d.pass[0].mode & kHDecode))  // fused: k_huff_write (+ k_idct_list) / k_band_dec
-      for (uint32_t it = 0; it < items; it += idct_thread_ ? kIdctItemStride : 1u) b.lists[L_IDCT].push_back({I, it});
+      for (uint32_t it = 0; it < items; it += opt_.idct_thread ? kIdctItemStride : 1u) b.lists[L_IDCT].push_back({I, it});
     if (d.ncomp >= 3 && !d.color_fused) {  // the RGB image: k_color, or k_cmyk for four components
       uint32_t q = (d.width + 7) / 8 * d.height;
       for (uint32_t it = 0; it < q; it += 256) b.lists[d.ncomp == 4 ? L_CMYK : L_COLOR].push_back({I, it});
@@ -1589,7 +1589,7 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
     const ResizePass &ps = d.pass[0];
     const uint32_t tiles = (ps.width + kDecCols - 1) / kDecCols;
     const uint32_t strips = (ps.row0 + ps.rows + 15) / 16 - ps.row0 / 16;
-    const uint32_t cnt = tiles * ((strips + dec_strips_ - 1) / dec_strips_);
+    const uint32_t cnt = tiles * ((strips + opt_.dec_strips - 1) / opt_.dec_strips);
     for (uint32_t it = 0; it < cnt; it++) cl.decl[(ps.mode & kHDecWide) ? 1 : 0].push_back({I, it});
   }
   for (int s = 0; s < kStages; s++) {
@@ -1620,20 +1620,20 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
       // the 8- and 16-tap kernels stage narrower segments (hseg_px in kernels.hip)
       while (cls < 2 && h_pass_span(ps) > (cls == 0 ? 192.0 : 384.0)) cls++;
       const int fused = (ps.mode & kHFused) ? 1 : 0;
-      const uint32_t ks = h_mfma_ ? h_mfma_steps(ps) : 0u;
+      const uint32_t ks = opt_.h_mfma ? h_mfma_steps(ps) : 0u;
       if (ks)
         for (uint32_t it = 0; it < cnt; it++) cl.hm[s / 2][fused][ks - 1].push_back({I, it});
       else
         for (uint32_t it = 0; it < cnt; it++) cl.hb[s / 2][fused][cls].push_back({I, it});
       if (fused && d.sem) b.h_zune = 1;  // the planar fused kernels of the zune fill classes
-    } else if (v_tile_ && (ps.src_stride & 15) == 0) {  // k_resize_vt: 4 waves of (R rows x 1 KiB) tiles
+    } else if (opt_.v_tile && (ps.src_stride & 15) == 0) {  // k_resize_vt: 4 waves of (R rows x 1 KiB) tiles
       const uint32_t units = (ps.width * ps.C + 15) / 16;
-      const uint32_t tiles = (units + 63) / 64 * ((ps.rows + v_tile_ - 1) / v_tile_);
+      const uint32_t tiles = (units + 63) / 64 * ((ps.rows + opt_.v_tile - 1) / opt_.v_tile);
       for (uint32_t it = 0; it < tiles; it += 4) b.lists[s == 1 ? L_RVT1 : L_RVT3].push_back({I, it});
-      b.v_tile = v_tile_;
+      b.v_tile = opt_.v_tile;
     } else {
       uint32_t cnt = (ps.width * ps.C + 15) / 16 * ps.rows;
-      for (uint32_t it = 0; it < cnt; it += 256 * v_units_) b.lists[L_RH0 + s].push_back({I, it});
+      for (uint32_t it = 0; it < cnt; it += 256 * opt_.v_units) b.lists[L_RH0 + s].push_back({I, it});
     }
   }
   if (d.copy_needed) {
@@ -1683,7 +1683,7 @@ dg_status Context::stage_and_upload(const SubmitArgs &a, Slot &sl, Batch &b, con
   char *P = (char *)sl.stage.p;
   memset(P + b.flags_off, 0, sizeof(BatchFlags));
   b.ptime_off = 0;
-  if (wg_timing_) {
+  if (opt_.wg_timing) {
     const size_t nrec = b.lists[L_SYNC].size() + b.lists[L_HUFF].size();
     b.ptime_off = b.pscans.empty() ? 0 : nrec * 16 + 64;  // per-scan {start, end} after the entropy records
     st = ensure(sl.wgt, nrec * 16 + 64 + b.pscans.size() * 16, sl.st);
@@ -1692,8 +1692,8 @@ dg_status Context::stage_and_upload(const SubmitArgs &a, Slot &sl, Batch &b, con
     bf->wgtime = (uint64_t)(uintptr_t)sl.wgt.p;
     bf->wgtime_write = (uint32_t)b.lists[L_SYNC].size();
   }
-  ((BatchFlags *)(P + b.flags_off))->debug = (uint32_t)(debug_flags_ >> 16) & 3u;
-  ((BatchFlags *)(P + b.flags_off))->prio = (uint32_t)entropy_prio_;
+  ((BatchFlags *)(P + b.flags_off))->debug = (uint32_t)(opt_.debug_flags >> 16) & 3u;
+  ((BatchFlags *)(P + b.flags_off))->prio = (uint32_t)opt_.entropy_prio;
   ((BatchFlags *)(P + b.flags_off))->idct_list = (uint64_t)(uintptr_t)((char *)sl.scratch.p + bl.idct_list_off);
   ((BatchFlags *)(P + b.flags_off))->idct_cap = b.idct_cap;
   memcpy(P + b.desc_off, b.descs.data(), b.descs.size() * sizeof(ImageDesc));
@@ -1707,7 +1707,7 @@ dg_status Context::stage_and_upload(const SubmitArgs &a, Slot &sl, Batch &b, con
     std::vector<CopyJob> ins;
     for (int i = 0; i < a.n; i++)
       if (b.desc_of[i] >= 0) ins.push_back({P + b.meta_bytes + bl.in_off[i], a.h_srcs[i], a.lens[i]});
-    parallel_copy(ins, copy_threads_);
+    parallel_copy(ins, opt_.copy_threads);
   }
   last_meta_bytes_ = b.meta_bytes;
   return DG_OK;
@@ -1717,15 +1717,15 @@ dg_status Context::stage_and_upload(const SubmitArgs &a, Slot &sl, Batch &b, con
 // finish() needs of the layout and of the caller's arrays is kept with the slot and the batch.
 dg_status Context::enqueue_upload(const SubmitArgs &a, Slot &sl, Batch &b, const BatchLayout &bl) {
   char *P = (char *)sl.stage.p;
-  if (timing_) HIPCHK(hipEventRecord(sl.ev[0], sl.st));
-  if (meta_pull_ >= 1) {
+  if (opt_.timing) HIPCHK(hipEventRecord(sl.ev[0], sl.st));
+  if (opt_.meta_pull >= 1) {
     launch_meta_pull(sl.st, P, sl.meta.p, b.meta_bytes);
     HIPCHK(hipGetLastError());
   } else {
     HIPCHK(hipMemcpyAsync(sl.meta.p, P, b.meta_bytes, hipMemcpyHostToDevice, sl.st));
   }
   if (a.host_io && bl.IN.off) {  // the coded inputs (dg_submit / dg_decode_one)
-    if (meta_pull_ >= 2) {  // off by default: dg_decode_one 18.1 -> 16.6 Gpx/s with it (profiles/r04/one_r4i)
+    if (opt_.meta_pull >= 2) {  // off by default: dg_decode_one 18.1 -> 16.6 Gpx/s with it (profiles/r04/one_r4i)
       launch_meta_pull(sl.st, P + b.meta_bytes, sl.input.p, bl.IN.off);
       HIPCHK(hipGetLastError());
     } else {
