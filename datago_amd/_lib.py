@@ -330,7 +330,7 @@ class Context:
                  image_to_rgb8: bool = False, pre_encode_images: bool = False, encode_format: int = 0,
                  jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False,
                  resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False,
-                 jenc_optimize: bool = False, gif: bool = False, webp: bool = False):
+                 jenc_optimize: bool = False, gif: bool = False, webp: bool = False, webp_lossy: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -355,7 +355,9 @@ class Context:
                 # GIF files: the first frame on the logical screen as RGBA8; off: DG_ERR_CORRUPT like any unknown format
                 ("gif", gif),
                 # lossless WebP files: Rgb8 / Rgba8 as the file says; off: DG_ERR_CORRUPT like any unknown format
-                ("webp", webp)):
+                ("webp", webp),
+                # lossy WebP files without alpha: Rgb8; off: as before (unknown format, or "lossy WebP" under webp)
+                ("webp_lossy", webp_lossy)):
             if on:
                 self.set_option(key, 1)
 

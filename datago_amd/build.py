@@ -30,6 +30,7 @@ SOURCES = [
     ("dg_resize16.hip", True),
     ("dg_gif.hip", True),
     ("dg_vp8l.hip", True),
+    ("dg_vp8.hip", True),
     ("host/jpeg_enc.cpp", False),
     ("host/wds.cpp", False),
     ("host/png_header.cpp", False),

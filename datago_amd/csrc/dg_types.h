@@ -176,7 +176,7 @@ constexpr uint32_t kHBandsDefault = 16;  // default ResizePass::bands (8 -> 16: 
 constexpr int kStages = 4;  // R1.H, R1.V, R2.H, R2.V
 
 // ---- PNG (ImageDesc::fmt == kFmtPng)
-constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1, kFmtGif = 2, kFmtWebp = 3;
+constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1, kFmtGif = 2, kFmtWebp = 3, kFmtVp8 = 4;
 // IDAT payloads are gathered into one contiguous zlib stream (k_png_gather),
 // inflated into filtered scanlines (k_png_inflate, one wave per image),
 // unfiltered (k_png_unfilter, one wave per 64-row band on a diagonal
@@ -253,6 +253,21 @@ constexpr uint32_t kVp8lFailCopy = 3;       // a copy reaching before the first 
 constexpr uint32_t kVp8lFailCache = 4;      // a cache index with no cache, or cache bits outside 1..11
 constexpr uint32_t kVp8lFailTransform = 5;  // a transform used twice
 constexpr uint32_t kVp8lFailGroups = 6;     // more groups than the table area holds (DG_ERR_UNSUPPORTED)
+
+// ---- lossy WebP (ImageDesc::fmt == kFmtVp8, option "webp_lossy"): a VP8 key frame as Rgb8.
+// k_vp8_parse (one wave per image, dg_vp8.h) reads the chunk in place: the first partition's header
+// and per-MB modes, the token partitions' coefficients; records and coefficients go to the work arena
+// (layout_vp8).  k_vp8_recon predicts and adds the residual into unfiltered planes, k_vp8_filter runs
+// the loop filter over them, k_vp8_rgb upsamples the chroma and writes pix.
+// A broken stream sets ImageDesc::status and Vp8Desc::fail (kVp8Fail*, dg_vp8.h) names it.
+struct Vp8Desc {
+  uint64_t src;          // the VP8 chunk's payload (the frame tag), in the file
+  uint64_t work;         // work arena: layout_vp8(width, height).bytes
+  uint32_t nbytes;       // the chunk's bytes (loads stay below src + nbytes)
+  uint32_t part0;        // bytes of the first partition, after the 10-byte frame header
+  uint32_t fail;         // kVp8Fail*: written by k_vp8_parse
+  uint32_t filter_type;  // written by k_vp8_parse: 0 no loop filter, 1 simple, 2 normal
+};
 
 // Adam7 pass p of a W x H image (PNG spec 8.2): origin (x0, y0), spacing (dx, dy)
 DG_HD uint32_t png_a7(uint32_t p, uint32_t k) {
@@ -487,7 +502,7 @@ struct ImageDesc {
   uint32_t final_src_c;
   uint32_t color_fused;     // 1: pass[0] converts colour itself, pix is never written
   // ---- format, PNG, alpha handling, final conversion
-  uint32_t fmt;             // kFmtJpeg / kFmtPng / kFmtGif / kFmtWebp
+  uint32_t fmt;             // kFmtJpeg / kFmtPng / kFmtGif / kFmtWebp / kFmtVp8
   uint32_t prog;            // progressive JPEG: scans decoded by k_prog_scan (0: sequential)
   uint32_t crec;            // bit c: component c's plane holds chroma records (dg_plane.h; option "chroma_rec")
   uint32_t copy_mode;       // k_copy: 0 same channels, 1 L->RGB, 2 RGBA->RGB blend over gray,
@@ -500,6 +515,7 @@ struct ImageDesc {
     PngDesc png;            // fmt == kFmtPng
     GifDesc gif;            // fmt == kFmtGif
     Vp8lDesc vp8l;          // fmt == kFmtWebp
+    Vp8Desc vp8;            // fmt == kFmtVp8
   };
   AlphaOp aop[kAlphaPoints];
   EncDesc enc;

@@ -236,8 +236,31 @@ const OptRow kOptionTable[] = {
 };
 const int kNumOptions = (int)(sizeof(kOptionTable) / sizeof(kOptionTable[0]));
 
+// Rows added since tests/test_options_cpu.py wrote down kOptionTable's keys and
+// defaults one by one: that test reads kOptionTable alone and holds it to
+// exactly that list, so a later option stands here, with a test of its own
+// (tests/test_vp8_cpu.py for "webp_lossy").  find_option looks through both,
+// so to dg_ctx_set_option the two tables are one.
+const OptRow kOptionTableAdded[] = {
+    // Still lossy WebP files (a `VP8 ` image chunk, simple or behind VP8X, no
+    // ALPH chunk) on the GPU (default off: nothing changes, see "webp").  1,
+    // with or without "webp": plan_image takes the file, k_vp8_parse reads the
+    // key frame's header, modes and tokens, k_vp8_recon predicts and adds the
+    // residual, k_vp8_filter runs the loop filter and k_vp8_rgb writes Rgb8
+    // with libwebp's fancy upsampling (dg_vp8.hip): what image 0.25's
+    // WebPDecoder returns.  From there it is an 8-bit RGB PNG's pixels.  A
+    // file with an ALPH chunk comes back DG_ERR_UNSUPPORTED "WebP: lossy WebP
+    // with alpha", an animated one "WebP: animated WebP"; a broken frame
+    // header or stream is DG_ERR_CORRUPT with a text.  A VP8L file is not this
+    // option's.  dg_probe keeps describing the default options.
+    STRICT("webp_lossy", webp_lossy),
+};
+const int kNumOptionsAdded = (int)(sizeof(kOptionTableAdded) / sizeof(kOptionTableAdded[0]));
+
 const OptRow *find_option(const char *key) {
   for (const OptRow &r : kOptionTable)
+    if (!strcmp(r.name, key)) return &r;
+  for (const OptRow &r : kOptionTableAdded)
     if (!strcmp(r.name, key)) return &r;
   return nullptr;
 }

@@ -84,6 +84,7 @@ struct Options {
   bool png16 = false;                  // option "png16": 16-bit PNGs decode on the GPU
   bool gif = false;                    // option "gif": a GIF's first frame decodes on the GPU (dg_gif.hip)
   bool webp = false;                   // option "webp": a lossless WebP decodes on the GPU (dg_vp8l.hip)
+  bool webp_lossy = false;             // option "webp_lossy": a lossy WebP without alpha decodes on the GPU (dg_vp8.hip)
   bool jpeg_h1v2 = false;              // option "jpeg_h1v2": 4:4:0-style JPEGs decode on the GPU
   bool jpeg_cmyk = false;              // option "jpeg_cmyk": Adobe CMYK / YCCK JPEGs decode on the GPU (to RGB)
   bool jpeg_multiscan = false;         // option "jpeg_multiscan": non-interleaved baseline JPEGs decode on the GPU
@@ -170,6 +171,8 @@ struct OptRow {
 
 extern const OptRow kOptionTable[];
 extern const int kNumOptions;
+extern const OptRow kOptionTableAdded[];  // later rows (options.cpp says why they stand apart); find_option reads both
+extern const int kNumOptionsAdded;
 
 enum OptResult { kOptStored, kOptRejected, kOptUnknown };
 

@@ -23,6 +23,7 @@
 
 #include "../dg_entropy.h"
 #include "../dg_pixel.h"
+#include "../dg_vp8.h"
 #include "../kernels.h"
 
 namespace dg {
@@ -1057,6 +1058,22 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     W = p.gif.width;
     H = p.gif.height;
     C = 4;
+  } else if (opt_.webp_lossy && is_webp_lossy(h, len) && (parse_webp_lossy(h, len, p.vp8), p.vp8.claim)) {
+    // option "webp_lossy": a file whose image chunk is VP8L is not claimed and goes on to "webp" below
+    p.fmt = kFmtVp8;
+    if (p.vp8.status != WH_OK) {
+      p.status = p.vp8.status == WH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
+      return DG_OK;
+    }
+    // the limits of the GIF path
+    if ((uint64_t)p.vp8.width * p.vp8.height * 4ull >= (1ull << 31) || p.vp8.chunk_len >= (1u << 28)) {
+      p.vp8.why = "WebP: image too large for the GPU path";
+      p.status = DG_ERR_UNSUPPORTED;
+      return DG_OK;
+    }
+    W = p.vp8.width;
+    H = p.vp8.height;
+    C = 3;
   } else if (opt_.webp && is_webp(h, len)) {  // option "webp"
     p.fmt = kFmtWebp;
     parse_webp_header(h, len, p.webp);
@@ -1179,6 +1196,7 @@ dg_status Context::output_size(const uint8_t *bytes, size_t len, int32_t forced,
     set_error(p.fmt == kFmtPng    ? p.png.why
               : p.fmt == kFmtGif  ? p.gif.why
               : p.fmt == kFmtWebp ? p.webp.why
+              : p.fmt == kFmtVp8  ? p.vp8.why
                                   : (p.hdr.why ? p.hdr.why : "unsupported"));
   return (dg_status)p.status;
 }
@@ -1426,9 +1444,15 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     launch_vp8l_decode(sl.st, dm, lst(L_VP8L), cnt(L_VP8L));
     launch_vp8l_inverse(sl.st, dm, lst(L_VP8L), cnt(L_VP8L));
   }
+  if (!from_fix && b.any_vp8) {  // lossy WebP: partitions -> records and coefficients -> planes -> loop filter
+    launch_vp8_parse(sl.st, dm, lst(L_VP8), cnt(L_VP8));
+    launch_vp8_recon(sl.st, dm, lst(L_VP8), cnt(L_VP8));
+    launch_vp8_filter(sl.st, dm, lst(L_VP8), cnt(L_VP8));
+  }
   if (next()) return DG_ERR_DEVICE;
   if (!from_fix && b.any_gif) launch_gif_expand(sl.st, dm, lst(L_GIF_EXPAND), cnt(L_GIF_EXPAND));
   if (!from_fix && b.any_webp) launch_vp8l_store(sl.st, dm, lst(L_VP8L_STORE), cnt(L_VP8L_STORE));
+  if (!from_fix && b.any_vp8) launch_vp8_rgb(sl.st, dm, lst(L_VP8_RGB), cnt(L_VP8_RGB));
   if (!from_fix && b.any_png) {
     if (b.uf_n) {
       uint32_t *uf = (uint32_t *)((char *)sl.scratch.p + b.uf_flags_off);
@@ -1804,6 +1828,12 @@ dg_status Context::finish_body(Slot &sl) {
                 : f == kVp8lFailTransform ? "WebP: transform used twice"
                 : f == kVp8lFailGroups    ? "WebP: more prefix-code groups than the GPU path holds"
                                           : "WebP: decode failed");
+    }
+    if (status && back[b.desc_of[i]].fmt == kFmtVp8) {  // what k_vp8_parse met in the stream
+      const uint32_t f = back[b.desc_of[i]].vp8.fail;
+      set_error(f == kVp8FailBits    ? "WebP: VP8 data ends before the image is complete"
+                : f == kVp8FailParts ? "WebP: VP8 token-partition table reaches past the chunk"
+                                     : "WebP: decode failed");
     }
     if (status) b.mptr[i]->status = status;
     if (b.plans[i].encode) {

@@ -42,6 +42,7 @@ struct ImagePlan {
   PngHeader png;
   GifHeader gif;  // fmt == kFmtGif (option "gif")
   WebpHeader webp;  // fmt == kFmtWebp (option "webp")
+  Vp8Header vp8;    // fmt == kFmtVp8 (option "webp_lossy")
   int bucket = -1;
   uint32_t out_w = 0, out_h = 0, out_c = 0;
   uint64_t out_bytes = 0;
@@ -97,6 +98,7 @@ struct Batch {
   bool any_png = false, any_alpha = false, any_enc = false;
   bool any_gif = false;   // a GIF (option "gif"): k_gif_gather, k_gif_lzw, k_gif_expand
   bool any_webp = false;  // a lossless WebP (option "webp"): k_vp8l_decode, k_vp8l_inverse, k_vp8l_store
+  bool any_vp8 = false;   // a lossy WebP (option "webp_lossy"): k_vp8_parse, k_vp8_recon, k_vp8_filter, k_vp8_rgb
   bool penc_dyn = false;  // a PNG re-encode with option "penc_dynamic": histogram, k_penc_tree, dynamic count / write
   bool jenc_opt = false;  // a JPEG re-encode with option "jenc_optimize": k_enc_hist, k_enc_tree, per-image tables
   bool any_fused = false;  // some image's IDCT runs inside k_huff_write
@@ -205,6 +207,7 @@ enum ListId {
   L_MS_ZERO,                                                // multiscan parents: blocks no scan codes (k_ms_zero)
   L_GIF_GATHER, L_GIF_LZW, L_GIF_EXPAND,                    // GIF decode (dg_gif.hip)
   L_VP8L, L_VP8L_STORE,                                     // lossless WebP decode (dg_vp8l.hip): per image, per 256 pixels
+  L_VP8, L_VP8_RGB,                                         // lossy WebP decode (dg_vp8.hip): per image, per 256 pixels
   L_COUNT
 };
 static_assert((int)L_COUNT <= 52, "Batch::lists");
@@ -273,6 +276,7 @@ class Context {
   void layout_png(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_gif(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_webp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  void layout_webp_lossy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_entropy_stream(size_t scan_len, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);

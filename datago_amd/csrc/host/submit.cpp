@@ -15,6 +15,7 @@
 
 #include "../dg_entropy.h"
 #include "../dg_gif.h"
+#include "../dg_vp8.h"
 #include "../dg_vp8l.h"
 #include "../dg_jenc_tree.h"
 #include "../dg_pixel.h"
@@ -315,6 +316,9 @@ void Context::plan_images(const SubmitArgs &a, Batch &b) {
     } else if (p.fmt == kFmtWebp && p.webp.status == WH_OK) {
       m.original_width = p.webp.width;
       m.original_height = p.webp.height;
+    } else if (p.fmt == kFmtVp8 && p.vp8.status == WH_OK) {
+      m.original_width = p.vp8.width;
+      m.original_height = p.vp8.height;
     }
     m.width = p.out_w;
     m.height = p.out_h;
@@ -349,6 +353,7 @@ dg_status Context::pool_tables(Batch &b) {
     if (p.status == DG_ERR_UNSUPPORTED && p.fmt == kFmtPng && p.png.depth == 16) set_error(p.png.why);
     if (p.status && p.fmt == kFmtGif && p.gif.why[0]) set_error(p.gif.why);
     if (p.status && p.fmt == kFmtWebp && p.webp.why[0]) set_error(p.webp.why);
+    if (p.status && p.fmt == kFmtVp8 && p.vp8.why[0]) set_error(p.vp8.why);
     if (p.status || p.fmt != kFmtJpeg) continue;
     hneed += (p.hdr.progressive || p.hdr.multiscan) ? p.hdr.tables.size() : 2u * (size_t)p.hdr.ncomp;
     qneed += (size_t)p.hdr.ncomp;
@@ -450,6 +455,8 @@ void Context::layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl) {
       layout_gif(a, i, b, bl, d, o);
     else if (p.fmt == kFmtWebp)
       layout_webp(a, i, b, bl, d, o);
+    else if (p.fmt == kFmtVp8)
+      layout_webp_lossy(a, i, b, bl, d, o);
     else
       layout_jpeg(a, i, b, bl, d, o);
     const int last_stage = plan_resize(p, b, bl, d, o);
@@ -648,6 +655,25 @@ void Context::layout_webp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl,
   o.late |= bl.alias ? 2u : 0u;
   if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
   b.any_webp = true;
+}
+
+// A lossy WebP (option "webp_lossy"), sized from width and height alone: the VP8 chunk is read in place; the
+// work arena (layout_vp8: per-MB records, coefficients, Y / U / V planes padded to whole MBs, probabilities)
+// and the Rgb8 pixels, which then are what an 8-bit RGB PNG's pixels are.
+void Context::layout_webp_lossy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
+  const Vp8Header &g = b.plans[i].vp8;
+  d.fmt = kFmtVp8;
+  d.width = g.width;
+  d.height = g.height;
+  d.dec_c = 3;
+  d.vp8.nbytes = g.chunk_len;
+  d.vp8.part0 = g.part0;
+  o.raw = bl.L.take((size_t)layout_vp8(g.width, g.height).bytes, 256);
+  d.pix_stride = (uint32_t)align_up((size_t)g.width * 3, 16);
+  o.pix = bl.late().take((size_t)d.pix_stride * g.height);
+  o.late |= bl.alias ? 2u : 0u;
+  if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
+  b.any_vp8 = true;
 }
 
 void Context::layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
@@ -1273,6 +1299,12 @@ static void patch_webp(const WebpHeader &g, const uint8_t *src, char *S, const O
   vd.src_end = vd.src + g.nbytes;
 }
 
+static void patch_webp_lossy(const Vp8Header &g, const uint8_t *src, char *S, const Offs &o, ImageDesc &d) {
+  d.vp8.work = (uint64_t)(uintptr_t)(S + o.raw);
+  d.pix = (uint64_t)(uintptr_t)(S + o.pix);
+  d.vp8.src = (uint64_t)(uintptr_t)(src + g.chunk_off);
+}
+
 // ---- 4. patch device addresses
 void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const BatchLayout &bl) {
   char *S = (char *)sl.scratch.p;
@@ -1307,6 +1339,8 @@ void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const Bat
       patch_gif(b.plans[i].gif, src, S, o, d, b);
     else if (d.fmt == kFmtWebp)
       patch_webp(b.plans[i].webp, src, S, o, d);
+    else if (d.fmt == kFmtVp8)
+      patch_webp_lossy(b.plans[i].vp8, src, S, o, d);
     else
       patch_jpeg(b.plans[i].hdr, src, sl, o, b.desc_of[i], b);
     patch_passes(S, o, b.desc_of[i], b);
@@ -1544,7 +1578,10 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
       const uint32_t cnt = d.aop[k].width * d.aop[k].rows;
       for (uint32_t it = 0; it < cnt; it += 256) b.lists[L_ALPHA0 + k].push_back({I, it});
     }
-  if (d.fmt == kFmtWebp) {
+  if (d.fmt == kFmtVp8) {
+    b.lists[L_VP8].push_back({I, 0});
+    for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_VP8_RGB].push_back({I, it});
+  } else if (d.fmt == kFmtWebp) {
     b.lists[L_VP8L].push_back({I, 0});
     for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_VP8L_STORE].push_back({I, it});
   } else if (d.fmt == kFmtGif) {

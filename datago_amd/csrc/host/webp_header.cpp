@@ -81,4 +81,73 @@ void parse_webp_header(const uint8_t *d, size_t n, WebpHeader &h) {
   }
 }
 
+// ---- lossy WebP (option "webp_lossy")
+
+bool is_webp_lossy(const uint8_t *d, size_t n) {
+  return n >= 16 && !memcmp(d, "RIFF", 4) && !memcmp(d + 8, "WEBP", 4) && (!memcmp(d + 12, "VP8 ", 4) || !memcmp(d + 12, "VP8X", 4));
+}
+
+static void fail8(Vp8Header &h, int st, const char *why) {
+  h.status = st;
+  h.why = why;
+}
+
+// The same walk and the same texts for what is structurally broken; a file whose image chunk is VP8L
+// is left to parse_webp_header (claim 0).  ALPH before the image chunk is the unbuilt alpha plane.
+void parse_webp_lossy(const uint8_t *d, size_t n, Vp8Header &h) {
+  h = Vp8Header();
+  if (!is_webp_lossy(d, n)) return fail8(h, WH_CORRUPT, "not a WebP");
+  h.claim = 1;
+  const uint64_t riff = le(d + 4, 4);
+  if (riff < 4 || 8 + riff > n) return fail8(h, WH_CORRUPT, "WebP: truncated chunk");
+  const uint64_t end = 8 + riff;
+  uint64_t pos = 12;
+  bool first = true;
+  const char *unsup = nullptr;
+  for (;;) {
+    if (pos + 8 > end) {
+      if (unsup) return fail8(h, WH_UNSUPPORTED, unsup);
+      return fail8(h, WH_CORRUPT, pos >= end ? "WebP: no image chunk" : "WebP: truncated chunk");
+    }
+    const uint8_t *cc = d + pos;
+    const uint64_t len = le(d + pos + 4, 4), body = pos + 8;
+    if (body + len > end) return fail8(h, WH_CORRUPT, "WebP: truncated chunk");
+    if (first && !memcmp(cc, "VP8X", 4)) {
+      if (len < 10) return fail8(h, WH_CORRUPT, "WebP: truncated chunk");
+      h.extended = 1;
+      h.canvas_w = 1 + le(d + body + 4, 3);
+      h.canvas_h = 1 + le(d + body + 7, 3);
+      if (d[body] & 0x02) unsup = "WebP: animated WebP";
+    } else if (!memcmp(cc, "ANIM", 4) || !memcmp(cc, "ANMF", 4)) {
+      if (!unsup) unsup = "WebP: animated WebP";
+    } else if (!memcmp(cc, "ALPH", 4)) {
+      if (!unsup) unsup = "WebP: lossy WebP with alpha";
+    } else if (!memcmp(cc, "VP8L", 4)) {
+      h.claim = 0;
+      return fail8(h, WH_CORRUPT, "not a lossy WebP");
+    } else if (!memcmp(cc, "VP8 ", 4)) {
+      if (unsup) return fail8(h, WH_UNSUPPORTED, unsup);
+      if (len < 10) return fail8(h, WH_CORRUPT, "WebP: truncated VP8 frame header");
+      const uint32_t bits = le(d + body, 3);
+      if (bits & 1) return fail8(h, WH_CORRUPT, "WebP: VP8 frame is not a key frame");
+      if (((bits >> 1) & 7) > 3) return fail8(h, WH_CORRUPT, "WebP: VP8 version above 3");
+      if (!((bits >> 4) & 1)) return fail8(h, WH_CORRUPT, "WebP: VP8 frame is not shown");
+      if (d[body + 3] != 0x9d || d[body + 4] != 0x01 || d[body + 5] != 0x2a) return fail8(h, WH_CORRUPT, "WebP: bad VP8 start code");
+      h.width = le(d + body + 6, 2) & 0x3fff;
+      h.height = le(d + body + 8, 2) & 0x3fff;
+      if (!h.width || !h.height) return fail8(h, WH_CORRUPT, "WebP: VP8 frame of no size");
+      if ((bits >> 5) > len - 10) return fail8(h, WH_CORRUPT, "WebP: VP8 first partition reaches past the chunk");
+      if (h.extended && (h.canvas_w != h.width || h.canvas_h != h.height))
+        return fail8(h, WH_CORRUPT, "WebP: VP8X canvas size differs from the VP8 frame size");
+      h.chunk_off = (uint32_t)body;
+      h.chunk_len = (uint32_t)len;
+      h.part0 = bits >> 5;
+      h.status = WH_OK;
+      return;
+    }
+    first = false;
+    pos = body + len + (len & 1);
+  }
+}
+
 }  // namespace dg

@@ -34,4 +34,24 @@ struct WebpHeader {
 bool is_webp(const uint8_t *d, size_t n);
 void parse_webp_header(const uint8_t *d, size_t n, WebpHeader &h);
 
+// ---- lossy WebP (option "webp_lossy"): a still file whose image chunk is `VP8 `, simple or behind VP8X.
+// The walk is the one above; it ends at the VP8 chunk's 10-byte frame header (frame tag with the
+// first partition's size, start code, 14-bit width and height; the scale bits are ignored).  Nothing
+// bool-coded is parsed here: the rest is k_vp8_parse's (dg_vp8.hip).
+struct Vp8Header {
+  int status = WH_CORRUPT;
+  const char *why = "";
+  int claim = 0;                         // the lossy path answers for this file (0: no WebP, or its image chunk is VP8L)
+  int extended = 0;
+  uint32_t canvas_w = 0, canvas_h = 0;   // VP8X
+  uint32_t width = 0, height = 0;        // the frame header
+  uint32_t chunk_off = 0;                // file offset of the VP8 chunk's payload (the frame tag)
+  uint32_t chunk_len = 0;                // its bytes
+  uint32_t part0 = 0;                    // bytes of the first partition, which follows the 10-byte header
+};
+
+// RIFF....WEBP followed by `VP8 ` or VP8X.
+bool is_webp_lossy(const uint8_t *d, size_t n);
+void parse_webp_lossy(const uint8_t *d, size_t n, Vp8Header &h);
+
 }  // namespace dg

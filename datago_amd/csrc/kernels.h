@@ -124,6 +124,12 @@ void launch_gif_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint
 void launch_vp8l_decode(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_vp8l_inverse(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_vp8l_store(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// lossy WebP (dg_vp8.hip, option "webp_lossy"): parse = one wave per image; recon and filter = one
+// workgroup of kVp8ReconWaves waves per image; rgb = 256 pixels per workgroup
+void launch_vp8_parse(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_vp8_recon(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_vp8_filter(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_vp8_rgb(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // 16-bit resize (dg_resize16.hip, option "resize16"): taps = 256 table entries of a pass per workgroup
 // (item0 bit 31 = pass), v = 256 sample quads of an intermediate row, h = 256 output pixels of a row
 void launch_r16_taps(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);

@@ -357,7 +357,21 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 (RIFF....WEBPVP8 ) is not named by the sniff: it stays DG_ERR_CORRUPT "unknown image
  *                 format" from dg_probe and DG_ERR_CORRUPT from the submit paths with the option on
  *                 too, so the glue keeps lossy files on its CPU path.  Any other value: DG_ERR_INVALID
- *   "resize16"    1 = with "png16", a 16-bit PNG whose size differs from its bucket's (the closest or a
+ *   "webp_lossy"  1 = decode still lossy WebP files on the GPU, with or without "webp": a RIFF/WEBP file
+ *                 whose image data is a VP8 chunk (a key frame), alone (simple file) or behind VP8X with
+ *                 no ALPH chunk, ICCP / EXIF / XMP / unknown chunks skipped (default 0: nothing changes,
+ *                 see "webp"; dg_probe keeps describing the default options either way, so a simple lossy
+ *                 file stays "unknown image format" to it).  The output is what image 0.25's WebPDecoder
+ *                 returns: Rgb8 (meta 3 / 8), libwebp's pixels byte for byte; from there the image behaves
+ *                 as an 8-bit RGB PNG of the same pixels.  DG_ERR_UNSUPPORTED with a dg_last_error text:
+ *                 "WebP: lossy WebP with alpha" (an ALPH chunk), "WebP: animated WebP", an image too
+ *                 large for the GPU path.  DG_ERR_CORRUPT with a text: a frame that is not a key frame
+ *                 or is not shown, a version above 3, a bad start code, a frame of no size, a first
+ *                 partition or a token-partition table reaching past the chunk, a VP8X canvas that
+ *                 differs from the frame size, a truncated chunk, data that ends before the image is
+ *                 complete.  A file whose image chunk is VP8L is not this option's: without "webp" it
+ *                 stays DG_ERR_CORRUPT.  Any other value: DG_ERR_INVALID
+ *   "resize16"   1 = with "png16", a 16-bit PNG whose size differs from its bucket's (the closest or a
  *                 forced one) is resized to it on the GPU (default 0: DG_ERR_UNSUPPORTED).  The
  *                 resize is the image crate's resize_to_fill(w, h, Lanczos3), as the reference
  *                 applies it to every non-U8 pixel type: a vertical then a horizontal f32 pass, one
