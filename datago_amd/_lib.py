@@ -330,7 +330,8 @@ class Context:
                  image_to_rgb8: bool = False, pre_encode_images: bool = False, encode_format: int = 0,
                  jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False,
                  resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False,
-                 jenc_optimize: bool = False, gif: bool = False, webp: bool = False, webp_lossy: bool = False):
+                 jenc_optimize: bool = False, gif: bool = False, webp: bool = False, webp_lossy: bool = False,
+                 webp_alpha: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -357,7 +358,9 @@ class Context:
                 # lossless WebP files: Rgb8 / Rgba8 as the file says; off: DG_ERR_CORRUPT like any unknown format
                 ("webp", webp),
                 # lossy WebP files without alpha: Rgb8; off: as before (unknown format, or "lossy WebP" under webp)
-                ("webp_lossy", webp_lossy)):
+                ("webp_lossy", webp_lossy),
+                # with webp_lossy, lossy WebP files with an ALPH chunk: Rgba8; off: DG_ERR_UNSUPPORTED "lossy WebP with alpha"
+                ("webp_alpha", webp_alpha)):
             if on:
                 self.set_option(key, 1)
 

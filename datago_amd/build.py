@@ -31,6 +31,7 @@ SOURCES = [
     ("dg_gif.hip", True),
     ("dg_vp8l.hip", True),
     ("dg_vp8.hip", True),
+    ("dg_alph.hip", True),
     ("host/jpeg_enc.cpp", False),
     ("host/wds.cpp", False),
     ("host/png_header.cpp", False),

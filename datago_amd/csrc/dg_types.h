@@ -246,6 +246,7 @@ struct Vp8lDesc {
   uint32_t xsize;        // ... the width of the decoded (packed) image in plane 0,
   uint32_t npal;         // ... and the colour table's entries
   uint32_t final_plane;  // written by k_vp8l_inverse: the plane that holds the ARGB image
+  uint32_t alph;         // 1: an ALPH chunk's stream (option "webp_alpha"): vp8l_walk's end-of-data rule for it
 };
 constexpr uint32_t kVp8lFailBits = 1;       // the data ends before the image is complete
 constexpr uint32_t kVp8lFailCode = 2;       // a prefix code neither complete nor single-symbol (or its description broken)
@@ -260,6 +261,10 @@ constexpr uint32_t kVp8lFailGroups = 6;     // more groups than the table area h
 // (layout_vp8).  k_vp8_recon predicts and adds the residual into unfiltered planes, k_vp8_filter runs
 // the loop filter over them, k_vp8_rgb upsamples the chroma and writes pix.
 // A broken stream sets ImageDesc::status and Vp8Desc::fail (kVp8Fail*, dg_vp8.h) names it.
+// With an ALPH chunk (option "webp_alpha") the image is Rgba8: k_alph_plane (dg_alph.hip) unfilters the
+// alpha plane from the chunk's raw bytes or from the green channel of a companion descriptor's VP8L
+// plane (fmt kFmtWebp, behind the batch's images: k_vp8l_decode / k_vp8l_inverse decode it through
+// their own list), and k_vp8_rgb stores it as the fourth channel.
 struct Vp8Desc {
   uint64_t src;          // the VP8 chunk's payload (the frame tag), in the file
   uint64_t work;         // work arena: layout_vp8(width, height).bytes
@@ -267,6 +272,12 @@ struct Vp8Desc {
   uint32_t part0;        // bytes of the first partition, after the 10-byte frame header
   uint32_t fail;         // kVp8Fail*: written by k_vp8_parse
   uint32_t filter_type;  // written by k_vp8_parse: 0 no loop filter, 1 simple, 2 normal
+  uint64_t alph_src;     // raw alpha: the ALPH payload after its header byte, in the file (0: VP8L-coded)
+  uint64_t alph_plane;   // the unfiltered alpha plane, width x height bytes (0: no alpha)
+  uint32_t alph_filter;  // kAlph* (dg_alph.h): none, horizontal, vertical, gradient
+  uint32_t alph_desc;    // VP8L-coded alpha: index of the companion descriptor
+  uint32_t alph_fail;    // written by k_alph_plane: the companion's status, when its stream failed
+  uint32_t pad_;
 };
 
 // Adam7 pass p of a W x H image (PNG spec 8.2): origin (x0, y0), spacing (dx, dy)

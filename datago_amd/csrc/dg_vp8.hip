@@ -5,7 +5,8 @@
 //   k_vp8_recon    intra prediction + inverse DCT into unfiltered Y / U / V planes, one
 //                  workgroup per image over the anti-diagonals x + 2y = d, one wave per MB
 //   k_vp8_filter   the loop filter, simple or normal, in place, with the same stepping
-//   k_vp8_rgb      fancy chroma upsampling + YUV -> RGB into pix, 256 pixels per workgroup
+//   k_vp8_rgb      fancy chroma upsampling + YUV -> RGB into pix, 256 pixels per workgroup; with an
+//                  alpha plane (option "webp_alpha", dg_alph.hip) RGBA, the plane's byte fourth
 //
 // What they restate: libwebp's VP8 decoder (tests/ref_vp8.py is the CPU form the tests
 // compare to); dg_vp8.h holds every statement of the walk, shared with the CPU emulation.
@@ -125,10 +126,11 @@ __global__ __launch_bounds__(256) void k_vp8_rgb(const ImageDesc *__restrict__ i
   const uint32_t y = idx / W, x = idx - y * W;
   Vp8Arena e = {gp<uint8_t>(im.vp8.work), threadIdx.x & 63u};
   const uint32_t p = vp8_rgb_px(e, layout_vp8(W, H), W, H, x, y);
-  DG_GLOBAL uint8_t *o = gp<uint8_t>(im.pix) + (size_t)y * im.pix_stride + (size_t)x * 3u;
+  DG_GLOBAL uint8_t *o = gp<uint8_t>(im.pix) + (size_t)y * im.pix_stride + (size_t)x * im.dec_c;
   o[0] = (uint8_t)p;
   o[1] = (uint8_t)(p >> 8);
   o[2] = (uint8_t)(p >> 16);
+  if (im.dec_c == 4u) o[3] = gp<const uint8_t>(im.vp8.alph_plane)[idx];
 }
 
 // ------------------------------------------------------------ launchers

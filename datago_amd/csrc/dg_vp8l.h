@@ -312,9 +312,11 @@ DG_HD uint32_t vp8l_read_groups(E &e, Vp8lBits &b, uint32_t n, uint32_t cache_bi
 
 // The entropy-coded pixels of a w x h image into the plane at word offset `dst` of the work arena.
 // meta: word offset of the entropy image (group = bits 8..23 of its pixels), or ~0 for one group.
+// lax_end (see vp8l_walk): the end of the data is looked for before each pixel or copy only, so the symbols
+// of the last one may read past it (zeros).
 template <class E>
 DG_HD uint32_t vp8l_pixels(E &e, Vp8lBits &b, uint64_t dst, uint32_t w, uint32_t h, uint32_t cache_bits, uint64_t meta,
-                           uint32_t meta_bits) {
+                           uint32_t meta_bits, bool lax_end = false) {
   const uint32_t n = w * h;
   const bool grouped = meta != ~0ull;
   const uint32_t mw = grouped ? vp8l_div_up(w, meta_bits) : 0u;
@@ -344,7 +346,7 @@ DG_HD uint32_t vp8l_pixels(E &e, Vp8lBits &b, uint64_t dst, uint32_t w, uint32_t
       const uint32_t len = vp8l_prefix_value(ls, vp8l_read(e, b, vp8l_prefix_extra(ls)));
       const uint32_t ds = vp8l_symbol(e, b, 4u);
       const uint32_t dist = vp8l_distance(w, vp8l_prefix_value(ds, vp8l_read(e, b, vp8l_prefix_extra(ds))));
-      if (vp8l_past(b)) return kVp8lFailBits;
+      if (vp8l_past(b) && !lax_end) return kVp8lFailBits;
       if (dist > pos || len > n - pos) return kVp8lFailCopy;
       e.copy(dst, pos, dist, len, cache_bits);
       adv = len;
@@ -361,7 +363,7 @@ DG_HD uint32_t vp8l_pixels(E &e, Vp8lBits &b, uint64_t dst, uint32_t w, uint32_t
       x %= w;
     }
   }
-  return vp8l_past(b) ? kVp8lFailBits : 0u;
+  return (vp8l_past(b) && !lax_end) ? kVp8lFailBits : 0u;
 }
 
 // A sub-image (transform data, entropy image, colour table): its own cache, one group, no prefix image.
@@ -383,8 +385,12 @@ struct Vp8lWalk {
 };
 
 // The whole stream after the 5-byte header: transforms, then the image into plane 0.
+// alph: the stream of an ALPH chunk (option "webp_alpha").  libwebp decodes such a stream through a path of
+// its own when the image is what its encoder writes for few alpha levels (colour indexing as the only
+// transform, no colour cache, one-symbol red, blue and alpha codes in every group), and that path looks for
+// the end of the data after each pixel or copy only while pixels are missing: vp8l_pixels' lax_end.
 template <class E>
-DG_HD uint32_t vp8l_walk(E &e, Vp8lBits &b, uint32_t w, uint32_t h, uint32_t groups_cap, Vp8lWalk &o) {
+DG_HD uint32_t vp8l_walk(E &e, Vp8lBits &b, uint32_t w, uint32_t h, uint32_t groups_cap, Vp8lWalk &o, bool alph = false) {
   o.ntrans = 0;
   o.npal = 0;
   o.xsize = w;
@@ -428,7 +434,15 @@ DG_HD uint32_t vp8l_walk(E &e, Vp8lBits &b, uint32_t w, uint32_t h, uint32_t gro
   if (ngroups > groups_cap) return kVp8lFailGroups;
   f = vp8l_read_groups(e, b, ngroups, cb);
   if (f) return f;
-  return vp8l_pixels(e, b, 0ull, xs, h, cb, meta, mbits);
+  bool lax_end = alph && o.ntrans == 1u && (o.trans[0] & 3u) == kVp8lIndex && !cb;
+  for (uint32_t g = 0; lax_end && g < ngroups; g++) {
+    e.select(g);
+    for (uint32_t k = 1; k < 4u; k++) {
+      const uint32_t ent = e.first(k, 0u);  // a one-symbol code: every entry valid with no bits
+      if (!(ent & kVp8lValid) || ((ent >> 16) & 15u)) lax_end = false;
+    }
+  }
+  return vp8l_pixels(e, b, 0ull, xs, h, cb, meta, mbits, lax_end);
 }
 
 // ------------------------------------------------------------ the predictor's wavefront

@@ -253,7 +253,7 @@ __global__ __launch_bounds__(64) void k_vp8l_decode(ImageDesc *__restrict__ imgs
   Vp8lBits b;
   vp8l_open(e, b, (uint32_t)(d.src & 3ull), d.nbytes);
   Vp8lWalk o;
-  const uint32_t fail = vp8l_walk(e, b, im.width, im.height, d.groups_cap, o);
+  const uint32_t fail = vp8l_walk(e, b, im.width, im.height, d.groups_cap, o, d.alph != 0u);
   if (threadIdx.x == 0) {
     im.vp8l.ntrans = o.ntrans;
     for (uint32_t i = 0; i < 4u; i++) im.vp8l.trans[i] = i < o.ntrans ? o.trans[i] : 0u;

@@ -239,7 +239,8 @@ const int kNumOptions = (int)(sizeof(kOptionTable) / sizeof(kOptionTable[0]));
 // Rows added since tests/test_options_cpu.py wrote down kOptionTable's keys and
 // defaults one by one: that test reads kOptionTable alone and holds it to
 // exactly that list, so a later option stands here, with a test of its own
-// (tests/test_vp8_cpu.py for "webp_lossy").  find_option looks through both,
+// (tests/test_vp8_cpu.py for "webp_lossy", tests/test_alph_cpu.py for
+// "webp_alpha").  find_option looks through both,
 // so to dg_ctx_set_option the two tables are one.
 const OptRow kOptionTableAdded[] = {
     // Still lossy WebP files (a `VP8 ` image chunk, simple or behind VP8X, no
@@ -254,6 +255,24 @@ const OptRow kOptionTableAdded[] = {
     // header or stream is DG_ERR_CORRUPT with a text.  A VP8L file is not this
     // option's.  dg_probe keeps describing the default options.
     STRICT("webp_lossy", webp_lossy),
+    // With "webp_lossy" (alone it changes nothing, and it does not need
+    // "webp"): a still lossy WebP whose VP8X alpha flag is set and which has
+    // exactly one ALPH chunk before its `VP8 ` chunk decodes to Rgba8 with
+    // non-premultiplied alpha, libwebp's MODE_RGBA bytes (default off: such a
+    // file stays DG_ERR_UNSUPPORTED "WebP: lossy WebP with alpha").  The RGB
+    // bytes are those of the `VP8 ` chunk alone.  The ALPH payload is a header
+    // byte and then the filtered plane, raw or as the green channel of a
+    // header-less VP8L stream, which k_vp8l_decode / k_vp8l_inverse decode
+    // through a companion descriptor whether or not "webp" is set;
+    // k_alph_plane (dg_alph.hip) undoes the horizontal, vertical or gradient
+    // filter and k_vp8_rgb stores the fourth channel.  From there the image is
+    // an RGBA8 PNG's pixels.  DG_ERR_CORRUPT with a text: a bad header byte, a
+    // chunk of fewer than 2 bytes, a raw plane shorter than the image, a VP8L
+    // alpha stream that does not decode.  DG_ERR_UNSUPPORTED with a text: a
+    // second ALPH chunk, an ALPH chunk in a file whose VP8X alpha flag is
+    // clear.  A file without an ALPH chunk before its image chunk decodes to
+    // Rgb8 as with "webp_lossy" alone, whatever its flag.
+    STRICT("webp_alpha", webp_alpha),
 };
 const int kNumOptionsAdded = (int)(sizeof(kOptionTableAdded) / sizeof(kOptionTableAdded[0]));
 

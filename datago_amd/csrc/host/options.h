@@ -85,6 +85,7 @@ struct Options {
   bool gif = false;                    // option "gif": a GIF's first frame decodes on the GPU (dg_gif.hip)
   bool webp = false;                   // option "webp": a lossless WebP decodes on the GPU (dg_vp8l.hip)
   bool webp_lossy = false;             // option "webp_lossy": a lossy WebP without alpha decodes on the GPU (dg_vp8.hip)
+  bool webp_alpha = false;             // option "webp_alpha": with "webp_lossy", a lossy WebP with an ALPH chunk decodes as Rgba8 (dg_alph.hip)
   bool jpeg_h1v2 = false;              // option "jpeg_h1v2": 4:4:0-style JPEGs decode on the GPU
   bool jpeg_cmyk = false;              // option "jpeg_cmyk": Adobe CMYK / YCCK JPEGs decode on the GPU (to RGB)
   bool jpeg_multiscan = false;         // option "jpeg_multiscan": non-interleaved baseline JPEGs decode on the GPU

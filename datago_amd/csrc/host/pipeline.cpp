@@ -1058,7 +1058,7 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     W = p.gif.width;
     H = p.gif.height;
     C = 4;
-  } else if (opt_.webp_lossy && is_webp_lossy(h, len) && (parse_webp_lossy(h, len, p.vp8), p.vp8.claim)) {
+  } else if (opt_.webp_lossy && is_webp_lossy(h, len) && (parse_webp_lossy(h, len, p.vp8, opt_.webp_alpha), p.vp8.claim)) {
     // option "webp_lossy": a file whose image chunk is VP8L is not claimed and goes on to "webp" below
     p.fmt = kFmtVp8;
     if (p.vp8.status != WH_OK) {
@@ -1073,7 +1073,7 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     }
     W = p.vp8.width;
     H = p.vp8.height;
-    C = 3;
+    C = (opt_.webp_alpha && p.vp8.has_alph) ? 4 : 3;  // option "webp_alpha"
   } else if (opt_.webp && is_webp(h, len)) {  // option "webp"
     p.fmt = kFmtWebp;
     parse_webp_header(h, len, p.webp);
@@ -1449,6 +1449,8 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     launch_vp8_recon(sl.st, dm, lst(L_VP8), cnt(L_VP8));
     launch_vp8_filter(sl.st, dm, lst(L_VP8), cnt(L_VP8));
   }
+  // their alpha planes, after the VP8L kernels have decoded the VP8L-coded ones
+  if (!from_fix && b.any_alph) launch_alph_plane(sl.st, dm, lst(L_ALPH), cnt(L_ALPH));
   if (next()) return DG_ERR_DEVICE;
   if (!from_fix && b.any_gif) launch_gif_expand(sl.st, dm, lst(L_GIF_EXPAND), cnt(L_GIF_EXPAND));
   if (!from_fix && b.any_webp) launch_vp8l_store(sl.st, dm, lst(L_VP8L_STORE), cnt(L_VP8L_STORE));
@@ -1829,11 +1831,15 @@ dg_status Context::finish_body(Slot &sl) {
                 : f == kVp8lFailGroups    ? "WebP: more prefix-code groups than the GPU path holds"
                                           : "WebP: decode failed");
     }
-    if (status && back[b.desc_of[i]].fmt == kFmtVp8) {  // what k_vp8_parse met in the stream
+    if (back[b.desc_of[i]].fmt == kFmtVp8 && !back[b.desc_of[i]].vp8.fail)  // a failed alpha stream fails its image
+      for (const Batch::AlphStream &as : b.alph_streams)
+        if (as.parent == b.desc_of[i] && back[as.desc].status > status) status = back[as.desc].status;
+    if (status && back[b.desc_of[i]].fmt == kFmtVp8) {  // what k_vp8_parse met in the stream, or k_vp8l_decode in the alpha's
       const uint32_t f = back[b.desc_of[i]].vp8.fail;
       set_error(f == kVp8FailBits    ? "WebP: VP8 data ends before the image is complete"
                 : f == kVp8FailParts ? "WebP: VP8 token-partition table reaches past the chunk"
-                                     : "WebP: decode failed");
+                : status == DG_ERR_UNSUPPORTED ? "WebP: ALPH stream with more prefix-code groups than the GPU path holds"
+                                               : "WebP: ALPH lossless stream does not decode");
     }
     if (status) b.mptr[i]->status = status;
     if (b.plans[i].encode) {

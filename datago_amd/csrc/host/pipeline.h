@@ -77,8 +77,8 @@ struct Batch {
   std::vector<ImageDesc> descs;
   std::vector<int> desc_of;           // image -> desc index or -1
   // workgroup lists (host copies) and their offsets in the device meta buffer
-  std::vector<WgItem> lists[52];
-  size_t list_off[52] = {0};
+  std::vector<WgItem> lists[53];
+  size_t list_off[53] = {0};
   // PNG: IDAT gather jobs and palettes, uploaded with the descriptors
   std::vector<GatherJob> gjobs;
   size_t gjob_off = 0;
@@ -97,7 +97,8 @@ struct Batch {
   size_t blob_off = 0;
   bool any_png = false, any_alpha = false, any_enc = false;
   bool any_gif = false;   // a GIF (option "gif"): k_gif_gather, k_gif_lzw, k_gif_expand
-  bool any_webp = false;  // a lossless WebP (option "webp"): k_vp8l_decode, k_vp8l_inverse, k_vp8l_store
+  bool any_webp = false;  // a lossless WebP (option "webp") or a VP8L-coded alpha stream: k_vp8l_decode, k_vp8l_inverse, k_vp8l_store
+  bool any_alph = false;  // a lossy WebP with an ALPH chunk (option "webp_alpha"): k_alph_plane
   bool any_vp8 = false;   // a lossy WebP (option "webp_lossy"): k_vp8_parse, k_vp8_recon, k_vp8_filter, k_vp8_rgb
   bool penc_dyn = false;  // a PNG re-encode with option "penc_dynamic": histogram, k_penc_tree, dynamic count / write
   bool jenc_opt = false;  // a JPEG re-encode with option "jenc_optimize": k_enc_hist, k_enc_tree, per-image tables
@@ -118,6 +119,13 @@ struct Batch {
     int image, scan;   // the image and its scan (JpegHeader::scans)
   };
   std::vector<MsScan> ms_scans;
+  // The companion descriptors of VP8L-coded alpha streams (option "webp_alpha"), behind the scan descriptors:
+  // fmt kFmtWebp with the image's width and height, on the L_VP8L list alone.
+  struct AlphStream {
+    int desc, parent;  // descriptor indices
+    int image;
+  };
+  std::vector<AlphStream> alph_streams;
   uint32_t max_slots = 1; // largest Huffman table count of an image (dynamic LDS of k_huff_sync/fix)
   uint32_t max_ac = 0;    // most distinct AC tables of a baseline JPEG (k_huff_sync multi-symbol lookups)
   size_t words_off = 0, words_bytes = 0;  // contiguous encoder bit buffers (zeroed per batch)
@@ -208,9 +216,10 @@ enum ListId {
   L_GIF_GATHER, L_GIF_LZW, L_GIF_EXPAND,                    // GIF decode (dg_gif.hip)
   L_VP8L, L_VP8L_STORE,                                     // lossless WebP decode (dg_vp8l.hip): per image, per 256 pixels
   L_VP8, L_VP8_RGB,                                         // lossy WebP decode (dg_vp8.hip): per image, per 256 pixels
+  L_ALPH,                                                   // its alpha plane (dg_alph.hip): per item of alph_items
   L_COUNT
 };
-static_assert((int)L_COUNT <= 52, "Batch::lists");
+static_assert((int)L_COUNT <= 53, "Batch::lists");
 
 // A recently pooled table (pool_huff / pool_quant): its key bytes and slot.
 struct RecentTab {
@@ -277,6 +286,7 @@ class Context {
   void layout_gif(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_webp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_webp_lossy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  void layout_alph_stream(int i, Batch &b, BatchLayout &bl);
   void layout_jpeg(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_entropy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_entropy_stream(size_t scan_len, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);

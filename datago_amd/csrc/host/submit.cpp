@@ -13,6 +13,7 @@
 #include <chrono>
 #include <cmath>
 
+#include "../dg_alph.h"
 #include "../dg_entropy.h"
 #include "../dg_gif.h"
 #include "../dg_vp8.h"
@@ -472,6 +473,39 @@ void Context::layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl) {
     if (p.status || p.fmt != kFmtJpeg || !p.hdr.multiscan) continue;
     for (int j = 0; j < (int)p.hdr.scans.size(); j++) layout_scan(i, j, b, bl);
   }
+  // likewise the companion descriptors of VP8L-coded alpha streams (option "webp_alpha")
+  for (int i = 0; b.any_alph && i < a.n; i++) {
+    const ImagePlan &p = b.plans[i];
+    if (!p.status && p.fmt == kFmtVp8 && b.descs[b.desc_of[i]].dec_c == 4 && alph_compression(p.vp8.alph_hdr) == kAlphVp8l)
+      layout_alph_stream(i, b, bl);
+  }
+}
+
+// The companion descriptor of image i's VP8L-coded alpha stream: a lossless image of the frame's size whose
+// bitstream is the ALPH payload after its header byte, with a work arena and a table area of its own and no
+// pixels; k_alph_plane reads the green channel of its final plane.
+void Context::layout_alph_stream(int i, Batch &b, BatchLayout &bl) {
+  const Vp8Header &g = b.plans[i].vp8;
+  ImageDesc d;
+  memset(&d, 0, sizeof(d));
+  Offs o;
+  memset(&o, 0, sizeof(o));
+  for (int s_ = 0; s_ < kStages; s_++) o.pass_cache[s_] = -1;
+  d.fmt = kFmtWebp;
+  d.sample_bytes = 1;
+  d.width = g.width;
+  d.height = g.height;
+  Vp8lDesc &vd = d.vp8l;
+  vd.nbytes = g.alph_len - 1;
+  vd.groups_cap = vp8l_groups_cap(g.width, g.height);
+  vd.alph = 1;
+  o.raw = bl.L.take((size_t)vp8l_work_words(g.width, g.height) * 4, 256);
+  o.zs = bl.L.take((size_t)vd.groups_cap * kVp8lGroupWords * 4, 256);
+  b.descs[b.desc_of[i]].vp8.alph_desc = (uint32_t)b.descs.size();
+  b.alph_streams.push_back({(int)b.descs.size(), b.desc_of[i], i});
+  b.descs.push_back(d);
+  bl.offs.push_back(o);
+  b.any_webp = true;
 }
 
 // The entropy-only descriptor of scan j of multiscan image i (ScanMap, dg_types.h): a stream of its own with
@@ -665,11 +699,16 @@ void Context::layout_webp_lossy(const SubmitArgs &a, int i, Batch &b, BatchLayou
   d.fmt = kFmtVp8;
   d.width = g.width;
   d.height = g.height;
-  d.dec_c = 3;
+  d.dec_c = (opt_.webp_alpha && g.has_alph) ? 4 : 3;
   d.vp8.nbytes = g.chunk_len;
   d.vp8.part0 = g.part0;
   o.raw = bl.L.take((size_t)layout_vp8(g.width, g.height).bytes, 256);
-  d.pix_stride = (uint32_t)align_up((size_t)g.width * 3, 16);
+  if (d.dec_c == 4) {  // option "webp_alpha": the unfiltered plane, a whole number of dwords (k_alph_plane reads it back by dwords)
+    d.vp8.alph_filter = alph_filter(g.alph_hdr);
+    o.zs = bl.L.take(align_up((size_t)g.width * g.height, 4), 256);
+    b.any_alph = true;
+  }
+  d.pix_stride = (uint32_t)align_up((size_t)g.width * d.dec_c, 16);
   o.pix = bl.late().take((size_t)d.pix_stride * g.height);
   o.late |= bl.alias ? 2u : 0u;
   if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
@@ -1303,6 +1342,10 @@ static void patch_webp_lossy(const Vp8Header &g, const uint8_t *src, char *S, co
   d.vp8.work = (uint64_t)(uintptr_t)(S + o.raw);
   d.pix = (uint64_t)(uintptr_t)(S + o.pix);
   d.vp8.src = (uint64_t)(uintptr_t)(src + g.chunk_off);
+  if (d.dec_c == 4) {
+    d.vp8.alph_plane = (uint64_t)(uintptr_t)(S + o.zs);
+    if (alph_compression(g.alph_hdr) == kAlphRaw) d.vp8.alph_src = (uint64_t)(uintptr_t)(src + g.alph_off + 1);
+  }
 }
 
 // ---- 4. patch device addresses
@@ -1356,6 +1399,15 @@ void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const Bat
     d.ds = (uint64_t)(uintptr_t)(S + o.ds);
     d.mk = (uint64_t)(uintptr_t)(S + o.mk);
     d.chunk = (uint64_t)(uintptr_t)(S + o.chunk);
+  }
+  for (const Batch::AlphStream &as : b.alph_streams) {  // alpha streams: inside the parent's source, their own arenas
+    Vp8lDesc &vd = b.descs[as.desc].vp8l;
+    const Offs &o = bl.offs[as.desc];
+    const uint8_t *src = a.host_io ? (const uint8_t *)sl.input.p + bl.in_off[as.image] : a.d_srcs[as.image];
+    vd.work = (uint64_t)(uintptr_t)(S + o.raw);
+    vd.tabs = (uint64_t)(uintptr_t)(S + o.zs);
+    vd.src = (uint64_t)(uintptr_t)(src + b.plans[as.image].vp8.alph_off + 1);
+    vd.src_end = vd.src + vd.nbytes;
   }
 }
 
@@ -1578,8 +1630,14 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
       const uint32_t cnt = d.aop[k].width * d.aop[k].rows;
       for (uint32_t it = 0; it < cnt; it += 256) b.lists[L_ALPHA0 + k].push_back({I, it});
     }
+  if (d.fmt == kFmtWebp && !d.dec_c) {  // an alpha stream's companion descriptor: the VP8L decode only
+    b.lists[L_VP8L].push_back({I, 0});
+    return;
+  }
   if (d.fmt == kFmtVp8) {
     b.lists[L_VP8].push_back({I, 0});
+    if (d.dec_c == 4)
+      for (uint32_t it = 0; it < alph_items(d.vp8.alph_filter, d.width, d.height); it++) b.lists[L_ALPH].push_back({I, it});
     for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_VP8_RGB].push_back({I, it});
   } else if (d.fmt == kFmtWebp) {
     b.lists[L_VP8L].push_back({I, 0});

@@ -9,6 +9,8 @@
 
 #include <string.h>
 
+#include "../dg_alph.h"
+
 namespace dg {
 
 bool is_webp(const uint8_t *d, size_t n) {
@@ -93,8 +95,9 @@ static void fail8(Vp8Header &h, int st, const char *why) {
 }
 
 // The same walk and the same texts for what is structurally broken; a file whose image chunk is VP8L
-// is left to parse_webp_header (claim 0).  ALPH before the image chunk is the unbuilt alpha plane.
-void parse_webp_lossy(const uint8_t *d, size_t n, Vp8Header &h) {
+// is left to parse_webp_header (claim 0).  ALPH before the image chunk is the alpha plane of option
+// "webp_alpha"; without the option the file is refused as before.
+void parse_webp_lossy(const uint8_t *d, size_t n, Vp8Header &h, bool alpha) {
   h = Vp8Header();
   if (!is_webp_lossy(d, n)) return fail8(h, WH_CORRUPT, "not a WebP");
   h.claim = 1;
@@ -117,11 +120,22 @@ void parse_webp_lossy(const uint8_t *d, size_t n, Vp8Header &h) {
       h.extended = 1;
       h.canvas_w = 1 + le(d + body + 4, 3);
       h.canvas_h = 1 + le(d + body + 7, 3);
+      h.alpha_flag = (d[body] & 0x10) ? 1 : 0;
       if (d[body] & 0x02) unsup = "WebP: animated WebP";
     } else if (!memcmp(cc, "ANIM", 4) || !memcmp(cc, "ANMF", 4)) {
       if (!unsup) unsup = "WebP: animated WebP";
     } else if (!memcmp(cc, "ALPH", 4)) {
-      if (!unsup) unsup = "WebP: lossy WebP with alpha";
+      if (!alpha) {
+        if (!unsup) unsup = "WebP: lossy WebP with alpha";
+      } else if (h.has_alph) {  // libwebp refuses the file; image-webp's answer is not known here
+        if (!unsup) unsup = "WebP: more than one ALPH chunk";
+      }
+      if (!h.has_alph) {
+        h.has_alph = 1;
+        h.alph_off = (uint32_t)body;
+        h.alph_len = (uint32_t)len;
+        h.alph_hdr = len ? d[body] : 0u;
+      }
     } else if (!memcmp(cc, "VP8L", 4)) {
       h.claim = 0;
       return fail8(h, WH_CORRUPT, "not a lossy WebP");
@@ -139,6 +153,14 @@ void parse_webp_lossy(const uint8_t *d, size_t n, Vp8Header &h) {
       if ((bits >> 5) > len - 10) return fail8(h, WH_CORRUPT, "WebP: VP8 first partition reaches past the chunk");
       if (h.extended && (h.canvas_w != h.width || h.canvas_h != h.height))
         return fail8(h, WH_CORRUPT, "WebP: VP8X canvas size differs from the VP8 frame size");
+      if (alpha && h.has_alph) {
+        // libwebp decodes the plane whatever the flag says; the reference's decoder may not
+        if (!h.alpha_flag) return fail8(h, WH_UNSUPPORTED, "WebP: ALPH chunk in a file whose VP8X alpha flag is clear");
+        if (h.alph_len < 2) return fail8(h, WH_CORRUPT, "WebP: ALPH chunk of fewer than 2 bytes");
+        if (!alph_header_ok(h.alph_hdr)) return fail8(h, WH_CORRUPT, "WebP: bad ALPH header byte");
+        if (alph_compression(h.alph_hdr) == kAlphRaw && (uint64_t)h.alph_len - 1 < (uint64_t)h.width * h.height)
+          return fail8(h, WH_CORRUPT, "WebP: raw alpha plane shorter than the image");
+      }
       h.chunk_off = (uint32_t)body;
       h.chunk_len = (uint32_t)len;
       h.part0 = bits >> 5;

@@ -48,10 +48,21 @@ struct Vp8Header {
   uint32_t chunk_off = 0;                // file offset of the VP8 chunk's payload (the frame tag)
   uint32_t chunk_len = 0;                // its bytes
   uint32_t part0 = 0;                    // bytes of the first partition, which follows the 10-byte header
+  // the first ALPH chunk before the image chunk (recorded with either setting of "webp_alpha")
+  int has_alph = 0;
+  int alpha_flag = 0;                    // VP8X's alpha bit
+  uint32_t alph_off = 0;                 // file offset of its payload (the header byte)
+  uint32_t alph_len = 0;                 // its bytes
+  uint32_t alph_hdr = 0;                 // the header byte (0 when the chunk is empty)
 };
 
 // RIFF....WEBP followed by `VP8 ` or VP8X.
 bool is_webp_lossy(const uint8_t *d, size_t n);
-void parse_webp_lossy(const uint8_t *d, size_t n, Vp8Header &h);
+// alpha (option "webp_alpha"): a file with one ALPH chunk before its image chunk is taken, and the chunk
+// is held to the rules of dg_alph.h: a header byte of compression and pre-processing 0 or 1 with the reserved bits clear,
+// at least 2 bytes, and a raw plane of at least width x height bytes (DG_ERR_CORRUPT otherwise: libwebp
+// refuses these); a second ALPH chunk, or one in a file whose VP8X alpha flag is clear, is
+// DG_ERR_UNSUPPORTED.  Off, such a file is "WebP: lossy WebP with alpha" as before.
+void parse_webp_lossy(const uint8_t *d, size_t n, Vp8Header &h, bool alpha = false);
 
 }  // namespace dg

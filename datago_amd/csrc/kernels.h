@@ -130,6 +130,8 @@ void launch_vp8_parse(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint3
 void launch_vp8_recon(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_vp8_filter(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_vp8_rgb(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// its alpha plane (dg_alph.hip, option "webp_alpha"): one wave per item of alph_items (dg_alph.h)
+void launch_alph_plane(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // 16-bit resize (dg_resize16.hip, option "resize16"): taps = 256 table entries of a pass per workgroup
 // (item0 bit 31 = pass), v = 256 sample quads of an intermediate row, h = 256 output pixels of a row
 void launch_r16_taps(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);

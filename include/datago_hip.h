@@ -371,6 +371,22 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 differs from the frame size, a truncated chunk, data that ends before the image is
  *                 complete.  A file whose image chunk is VP8L is not this option's: without "webp" it
  *                 stays DG_ERR_CORRUPT.  Any other value: DG_ERR_INVALID
+ *   "webp_alpha"  1 = with "webp_lossy" (alone it changes nothing; it does not need "webp"), decode still
+ *                 lossy WebP files with alpha: a file whose VP8X alpha flag is set and which has exactly
+ *                 one ALPH chunk before its VP8 chunk (default 0: DG_ERR_UNSUPPORTED "WebP: lossy WebP
+ *                 with alpha", as before).  The output is libwebp's MODE_RGBA: Rgba8 (meta 4 / 8) with
+ *                 non-premultiplied alpha, the colour bytes those of the VP8 chunk alone; from there the
+ *                 image behaves as an RGBA8 PNG of the same pixels.  The ALPH payload is a header byte
+ *                 (compression 0 raw / 1 VP8L, filter none / horizontal / vertical / gradient,
+ *                 pre-processing 0 / 1) and the filtered plane; a VP8L-coded plane is decoded by the
+ *                 lossless kernels whether or not "webp" is set.  DG_ERR_CORRUPT with a dg_last_error
+ *                 text: "WebP: bad ALPH header byte", "WebP: ALPH chunk of fewer than 2 bytes", "WebP:
+ *                 raw alpha plane shorter than the image" (extra bytes are ignored), "WebP: ALPH
+ *                 lossless stream does not decode".  DG_ERR_UNSUPPORTED with a text: "WebP: more than
+ *                 one ALPH chunk", "WebP: ALPH chunk in a file whose VP8X alpha flag is clear", an alpha
+ *                 stream with more prefix-code groups than the GPU path holds.  A file without an ALPH
+ *                 chunk before its VP8 chunk is Rgb8 as with "webp_lossy" alone, whatever its flag.
+ *                 dg_probe keeps describing the default options.  Any other value: DG_ERR_INVALID
  *   "resize16"   1 = with "png16", a 16-bit PNG whose size differs from its bucket's (the closest or a
  *                 forced one) is resized to it on the GPU (default 0: DG_ERR_UNSUPPORTED).  The
  *                 resize is the image crate's resize_to_fill(w, h, Lanczos3), as the reference
