@@ -30,7 +30,7 @@ DG_OK, DG_ERR_UNSUPPORTED, DG_ERR_CORRUPT, DG_ERR_OOM, DG_ERR_BAD_BUCKET = 0, 1,
 DG_ERR_INVALID, DG_ERR_SMALL_BUFFER, DG_ERR_DEVICE, DG_ERR_NOT_READY = 5, 6, 7, 8
 STATUS_NAMES = {0: "OK", 1: "UNSUPPORTED", 2: "CORRUPT", 3: "OOM", 4: "BAD_BUCKET", 5: "INVALID",
                 6: "SMALL_BUFFER", 7: "DEVICE", 8: "NOT_READY"}
-DG_FMT_UNKNOWN, DG_FMT_JPEG, DG_FMT_PNG, DG_FMT_GIF, DG_FMT_WEBP = 0, 1, 2, 3, 4
+DG_FMT_UNKNOWN, DG_FMT_JPEG, DG_FMT_PNG, DG_FMT_GIF, DG_FMT_WEBP, DG_FMT_BMP = 0, 1, 2, 3, 4, 5
 
 # exported symbols (must match include/datago_hip.h; checked by tests)
 EXPORTS = [
@@ -331,7 +331,7 @@ class Context:
                  jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False,
                  resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False,
                  jenc_optimize: bool = False, gif: bool = False, webp: bool = False, webp_lossy: bool = False,
-                 webp_alpha: bool = False):
+                 webp_alpha: bool = False, bmp: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -360,7 +360,9 @@ class Context:
                 # lossy WebP files without alpha: Rgb8; off: as before (unknown format, or "lossy WebP" under webp)
                 ("webp_lossy", webp_lossy),
                 # with webp_lossy, lossy WebP files with an ALPH chunk: Rgba8; off: DG_ERR_UNSUPPORTED "lossy WebP with alpha"
-                ("webp_alpha", webp_alpha)):
+                ("webp_alpha", webp_alpha),
+                # Windows bitmaps: Rgb8, or Rgba8 with an alpha mask; off: DG_ERR_CORRUPT like any unknown format
+                ("bmp", bmp)):
             if on:
                 self.set_option(key, 1)
 

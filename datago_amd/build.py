@@ -29,6 +29,7 @@ SOURCES = [
     ("dg_band.hip", True),
     ("dg_resize16.hip", True),
     ("dg_gif.hip", True),
+    ("dg_bmp.hip", True),
     ("dg_vp8l.hip", True),
     ("dg_vp8.hip", True),
     ("dg_alph.hip", True),
@@ -36,6 +37,7 @@ SOURCES = [
     ("host/wds.cpp", False),
     ("host/png_header.cpp", False),
     ("host/gif_header.cpp", False),
+    ("host/bmp_header.cpp", False),
     ("host/webp_header.cpp", False),
     ("host/options.cpp", False),
     ("host/pipeline.cpp", False),

@@ -176,7 +176,7 @@ constexpr uint32_t kHBandsDefault = 16;  // default ResizePass::bands (8 -> 16: 
 constexpr int kStages = 4;  // R1.H, R1.V, R2.H, R2.V
 
 // ---- PNG (ImageDesc::fmt == kFmtPng)
-constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1, kFmtGif = 2, kFmtWebp = 3, kFmtVp8 = 4;
+constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1, kFmtGif = 2, kFmtWebp = 3, kFmtVp8 = 4, kFmtBmp = 5;
 // IDAT payloads are gathered into one contiguous zlib stream (k_png_gather),
 // inflated into filtered scanlines (k_png_inflate, one wave per image),
 // unfiltered (k_png_unfilter, one wave per 64-row band on a diagonal
@@ -226,6 +226,30 @@ struct GifDesc {
 constexpr uint32_t kGifFailCode = 1;     // a code above the next free one, or the next free one straight after a clear
 constexpr uint32_t kGifFailShort = 2;    // the data ends (or an end code comes) before fw x fh indices
 constexpr uint32_t kGifFailPalette = 3;  // an index at or past the colour table's size
+
+// ---- BMP (ImageDesc::fmt == kFmtBmp, option "bmp"): a Windows bitmap as Rgb8 / Rgba8, top row first.
+// An RLE8 / RLE4 stream is decoded by k_bmp_rle (one wave per image, dg_bmp.h) into a width x height
+// index plane in stream (bottom-up) row order; k_bmp_expand reads that plane or the file's own pixel
+// array and does the row flip, the palette lookup, BGR -> RGB and the mask byte selection.  Anything
+// irregular sets ImageDesc::status = DG_ERR_UNSUPPORTED and BmpDesc::fail names it.
+struct BmpDesc {
+  uint64_t src;       // the pixel array or the RLE stream in the file (any byte alignment)
+  uint64_t src_end;   // one past its last byte (loads stay below it)
+  uint64_t idx;       // RLE: the index plane, width x height bytes, rows in stream order
+  uint64_t pal;       // 256 x RGBA palette (device)
+  uint32_t bits;      // 1 / 4 / 8 / 24 / 32
+  uint32_t rle;       // 0, 1 = RLE8, 2 = RLE4
+  uint32_t stride;    // bytes per row of the pixel array
+  uint32_t top_down;
+  uint32_t npal;      // entries of the colour table
+  uint32_t pos;       // 24 / 32 bits: byte of R | G << 8 | B << 16 | A << 24 inside a pixel
+  uint32_t data_len;  // RLE: bytes of the stream
+  uint32_t fail;      // kBmpFail*: written by k_bmp_rle / k_bmp_expand
+};
+constexpr uint32_t kBmpFailRow = 1;      // a run or absolute block that passes (or starts past) its row's end
+constexpr uint32_t kBmpFailDelta = 2;    // a delta, an early end-of-line or an end-of-bitmap with pixels unwritten
+constexpr uint32_t kBmpFailShort = 3;    // the data ends before the last pixel
+constexpr uint32_t kBmpFailPalette = 4;  // an index at or past the colour table's size
 
 // ---- lossless WebP (ImageDesc::fmt == kFmtWebp, option "webp"): a VP8L chunk as Rgb8 / Rgba8.
 // k_vp8l_decode (one wave per image, dg_vp8l.h) reads the bitstream after the 5-byte header in place:
@@ -513,7 +537,7 @@ struct ImageDesc {
   uint32_t final_src_c;
   uint32_t color_fused;     // 1: pass[0] converts colour itself, pix is never written
   // ---- format, PNG, alpha handling, final conversion
-  uint32_t fmt;             // kFmtJpeg / kFmtPng / kFmtGif / kFmtWebp / kFmtVp8
+  uint32_t fmt;             // kFmtJpeg / kFmtPng / kFmtGif / kFmtWebp / kFmtVp8 / kFmtBmp
   uint32_t prog;            // progressive JPEG: scans decoded by k_prog_scan (0: sequential)
   uint32_t crec;            // bit c: component c's plane holds chroma records (dg_plane.h; option "chroma_rec")
   uint32_t copy_mode;       // k_copy: 0 same channels, 1 L->RGB, 2 RGBA->RGB blend over gray,
@@ -527,6 +551,7 @@ struct ImageDesc {
     GifDesc gif;            // fmt == kFmtGif
     Vp8lDesc vp8l;          // fmt == kFmtWebp
     Vp8Desc vp8;            // fmt == kFmtVp8
+    BmpDesc bmp;            // fmt == kFmtBmp
   };
   AlphaOp aop[kAlphaPoints];
   EncDesc enc;

@@ -229,6 +229,22 @@ dg_status dg_probe(const uint8_t *bytes, size_t len, dg_probe_info *out) {
     }
     return DG_OK;
   }
+  if (dg::is_bmp(bytes, len)) {
+    dg::BmpHeader h;
+    dg::parse_bmp_header(bytes, len, h);
+    out->format = DG_FMT_BMP;
+    out->width = h.width;
+    out->height = h.height;  // |biHeight|
+    out->components = h.out_c == 4 ? 4 : 3;  // Rgba8 for a bit-field file with an alpha mask, else Rgb8
+    out->bit_depth = 8;
+    out->precision = 8;
+    out->gpu_supported = 0;  // the default options (option "bmp" decodes it)
+    if (h.status == dg::BH_CORRUPT) {
+      dg::set_error(h.why);
+      return DG_ERR_CORRUPT;
+    }
+    return DG_OK;
+  }
   if (dg::is_webp(bytes, len)) {  // lossless or extended; a simple lossy file stays an unknown format
     dg::WebpHeader h;
     dg::parse_webp_header(bytes, len, h);

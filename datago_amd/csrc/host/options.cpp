@@ -240,7 +240,7 @@ const int kNumOptions = (int)(sizeof(kOptionTable) / sizeof(kOptionTable[0]));
 // defaults one by one: that test reads kOptionTable alone and holds it to
 // exactly that list, so a later option stands here, with a test of its own
 // (tests/test_vp8_cpu.py for "webp_lossy", tests/test_alph_cpu.py for
-// "webp_alpha").  find_option looks through both,
+// "webp_alpha", tests/test_bmp_cpu.py for "bmp").  find_option looks through both,
 // so to dg_ctx_set_option the two tables are one.
 const OptRow kOptionTableAdded[] = {
     // Still lossy WebP files (a `VP8 ` image chunk, simple or behind VP8X, no
@@ -273,6 +273,17 @@ const OptRow kOptionTableAdded[] = {
     // clear.  A file without an ALPH chunk before its image chunk decodes to
     // Rgb8 as with "webp_lossy" alone, whatever its flag.
     STRICT("webp_alpha", webp_alpha),
+    // Windows bitmaps on the GPU (default off: DG_ERR_CORRUPT like any format
+    // the library does not know).  1: plan_image takes a BMP; an RLE8 / RLE4
+    // stream is decoded by k_bmp_rle, and k_bmp_expand writes Rgb8, or Rgba8
+    // for a bit-field file with an alpha mask, top row first (dg_bmp.hip): what
+    // image 0.25's BmpDecoder returns for load_from_memory, for the files it
+    // and Pillow decode alike.  From there it is an 8-bit RGB / RGBA PNG's
+    // pixels.  16-bit files, the other forms the two decoders disagree on and
+    // stream irregularities come back DG_ERR_UNSUPPORTED with a dg_last_error
+    // text.  dg_probe names a BMP either way and keeps describing the default
+    // options.
+    STRICT("bmp", bmp),
 };
 const int kNumOptionsAdded = (int)(sizeof(kOptionTableAdded) / sizeof(kOptionTableAdded[0]));
 

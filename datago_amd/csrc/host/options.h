@@ -83,6 +83,7 @@ struct Options {
   bool progressive = true;             // option "progressive"
   bool png16 = false;                  // option "png16": 16-bit PNGs decode on the GPU
   bool gif = false;                    // option "gif": a GIF's first frame decodes on the GPU (dg_gif.hip)
+  bool bmp = false;                    // option "bmp": a Windows bitmap decodes on the GPU (dg_bmp.hip)
   bool webp = false;                   // option "webp": a lossless WebP decodes on the GPU (dg_vp8l.hip)
   bool webp_lossy = false;             // option "webp_lossy": a lossy WebP without alpha decodes on the GPU (dg_vp8.hip)
   bool webp_alpha = false;             // option "webp_alpha": with "webp_lossy", a lossy WebP with an ALPH chunk decodes as Rgba8 (dg_alph.hip)

@@ -1058,6 +1058,23 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     W = p.gif.width;
     H = p.gif.height;
     C = 4;
+  } else if (opt_.bmp && is_bmp(h, len)) {  // option "bmp"
+    p.fmt = kFmtBmp;
+    parse_bmp_header(h, len, p.bmp);
+    if (p.bmp.status != BH_OK) {
+      p.status = p.bmp.status == BH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
+      return DG_OK;
+    }
+    // the limits of the GIF path: the pixel buffer, the index plane and the stream stay 32-bit addressable
+    if ((uint64_t)p.bmp.width * p.bmp.height * 4ull >= (1ull << 31) || p.bmp.data_len >= (1ull << 31) ||
+        ((p.bmp.compression == BMP_RLE8 || p.bmp.compression == BMP_RLE4) && p.bmp.data_len >= (1ull << 28))) {
+      p.bmp.why = "BMP: image too large for the GPU path";
+      p.status = DG_ERR_UNSUPPORTED;
+      return DG_OK;
+    }
+    W = p.bmp.width;
+    H = p.bmp.height;
+    C = (uint32_t)p.bmp.out_c;
   } else if (opt_.webp_lossy && is_webp_lossy(h, len) && (parse_webp_lossy(h, len, p.vp8, opt_.webp_alpha), p.vp8.claim)) {
     // option "webp_lossy": a file whose image chunk is VP8L is not claimed and goes on to "webp" below
     p.fmt = kFmtVp8;
@@ -1195,6 +1212,7 @@ dg_status Context::output_size(const uint8_t *bytes, size_t len, int32_t forced,
   if (p.status)
     set_error(p.fmt == kFmtPng    ? p.png.why
               : p.fmt == kFmtGif  ? p.gif.why
+              : p.fmt == kFmtBmp  ? p.bmp.why
               : p.fmt == kFmtWebp ? p.webp.why
               : p.fmt == kFmtVp8  ? p.vp8.why
                                   : (p.hdr.why ? p.hdr.why : "unsupported"));
@@ -1440,6 +1458,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     launch_gif_gather(sl.st, (const GatherJob *)(M + b.gjob_off), lst(L_GIF_GATHER), cnt(L_GIF_GATHER));
     launch_gif_lzw(sl.st, dm, lst(L_GIF_LZW), cnt(L_GIF_LZW));
   }
+  if (!from_fix && b.any_bmp) launch_bmp_rle(sl.st, dm, lst(L_BMP_RLE), cnt(L_BMP_RLE));  // BMP: RLE stream -> index plane
   if (!from_fix && b.any_webp) {  // lossless WebP: bitstream -> ARGB plane -> inverse transforms
     launch_vp8l_decode(sl.st, dm, lst(L_VP8L), cnt(L_VP8L));
     launch_vp8l_inverse(sl.st, dm, lst(L_VP8L), cnt(L_VP8L));
@@ -1453,6 +1472,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   if (!from_fix && b.any_alph) launch_alph_plane(sl.st, dm, lst(L_ALPH), cnt(L_ALPH));
   if (next()) return DG_ERR_DEVICE;
   if (!from_fix && b.any_gif) launch_gif_expand(sl.st, dm, lst(L_GIF_EXPAND), cnt(L_GIF_EXPAND));
+  if (!from_fix && b.any_bmp) launch_bmp_expand(sl.st, dm, lst(L_BMP_EXPAND), cnt(L_BMP_EXPAND));
   if (!from_fix && b.any_webp) launch_vp8l_store(sl.st, dm, lst(L_VP8L_STORE), cnt(L_VP8L_STORE));
   if (!from_fix && b.any_vp8) launch_vp8_rgb(sl.st, dm, lst(L_VP8_RGB), cnt(L_VP8_RGB));
   if (!from_fix && b.any_png) {
@@ -1820,6 +1840,14 @@ dg_status Context::finish_body(Slot &sl) {
                 : f == kGifFailShort ? "GIF: image data ends before the frame is complete"
                 : f == kGifFailPalette ? "GIF: pixel index past the colour table"
                                        : "GIF: decode failed");
+    }
+    if (status && back[b.desc_of[i]].fmt == kFmtBmp) {  // what k_bmp_rle / k_bmp_expand met in the stream
+      const uint32_t f = back[b.desc_of[i]].bmp.fail;
+      set_error(f == kBmpFailRow       ? "BMP: RLE run or absolute block passes its row's end"
+                : f == kBmpFailDelta   ? "BMP: RLE delta, early end-of-line or end-of-bitmap leaves pixels unwritten"
+                : f == kBmpFailShort   ? "BMP: RLE data ends before the bitmap is complete"
+                : f == kBmpFailPalette ? "BMP: pixel index past the colour table"
+                                       : "BMP: decode failed");
     }
     if (status && back[b.desc_of[i]].fmt == kFmtWebp) {  // what k_vp8l_decode met in the stream
       const uint32_t f = back[b.desc_of[i]].vp8l.fail;

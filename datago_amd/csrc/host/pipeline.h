@@ -17,6 +17,7 @@
 #include "options.h"
 #include "jpeg_header.h"
 #include "gif_header.h"
+#include "bmp_header.h"
 #include "webp_header.h"
 #include "png_header.h"
 #include "jpeg_enc.h"
@@ -43,6 +44,7 @@ struct ImagePlan {
   GifHeader gif;  // fmt == kFmtGif (option "gif")
   WebpHeader webp;  // fmt == kFmtWebp (option "webp")
   Vp8Header vp8;    // fmt == kFmtVp8 (option "webp_lossy")
+  BmpHeader bmp;    // fmt == kFmtBmp (option "bmp")
   int bucket = -1;
   uint32_t out_w = 0, out_h = 0, out_c = 0;
   uint64_t out_bytes = 0;
@@ -77,8 +79,8 @@ struct Batch {
   std::vector<ImageDesc> descs;
   std::vector<int> desc_of;           // image -> desc index or -1
   // workgroup lists (host copies) and their offsets in the device meta buffer
-  std::vector<WgItem> lists[53];
-  size_t list_off[53] = {0};
+  std::vector<WgItem> lists[55];
+  size_t list_off[55] = {0};
   // PNG: IDAT gather jobs and palettes, uploaded with the descriptors
   std::vector<GatherJob> gjobs;
   size_t gjob_off = 0;
@@ -99,6 +101,7 @@ struct Batch {
   bool any_gif = false;   // a GIF (option "gif"): k_gif_gather, k_gif_lzw, k_gif_expand
   bool any_webp = false;  // a lossless WebP (option "webp") or a VP8L-coded alpha stream: k_vp8l_decode, k_vp8l_inverse, k_vp8l_store
   bool any_alph = false;  // a lossy WebP with an ALPH chunk (option "webp_alpha"): k_alph_plane
+  bool any_bmp = false;   // a BMP (option "bmp"): k_bmp_rle, k_bmp_expand
   bool any_vp8 = false;   // a lossy WebP (option "webp_lossy"): k_vp8_parse, k_vp8_recon, k_vp8_filter, k_vp8_rgb
   bool penc_dyn = false;  // a PNG re-encode with option "penc_dynamic": histogram, k_penc_tree, dynamic count / write
   bool jenc_opt = false;  // a JPEG re-encode with option "jenc_optimize": k_enc_hist, k_enc_tree, per-image tables
@@ -217,9 +220,10 @@ enum ListId {
   L_VP8L, L_VP8L_STORE,                                     // lossless WebP decode (dg_vp8l.hip): per image, per 256 pixels
   L_VP8, L_VP8_RGB,                                         // lossy WebP decode (dg_vp8.hip): per image, per 256 pixels
   L_ALPH,                                                   // its alpha plane (dg_alph.hip): per item of alph_items
+  L_BMP_RLE, L_BMP_EXPAND,                                  // BMP decode (dg_bmp.hip): per RLE image, per 64 groups of 4 pixels
   L_COUNT
 };
-static_assert((int)L_COUNT <= 53, "Batch::lists");
+static_assert((int)L_COUNT <= 55, "Batch::lists");
 
 // A recently pooled table (pool_huff / pool_quant): its key bytes and slot.
 struct RecentTab {
@@ -284,6 +288,7 @@ class Context {
   void layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl);  // per image: the next five
   void layout_png(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_gif(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
+  void layout_bmp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_webp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_webp_lossy(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o);
   void layout_alph_stream(int i, Batch &b, BatchLayout &bl);

@@ -15,6 +15,7 @@
 
 #include "../dg_alph.h"
 #include "../dg_entropy.h"
+#include "../dg_bmp.h"
 #include "../dg_gif.h"
 #include "../dg_vp8.h"
 #include "../dg_vp8l.h"
@@ -314,6 +315,9 @@ void Context::plan_images(const SubmitArgs &a, Batch &b) {
     } else if (p.fmt == kFmtGif && p.gif.status == GH_OK) {  // the logical screen
       m.original_width = p.gif.width;
       m.original_height = p.gif.height;
+    } else if (p.fmt == kFmtBmp && p.bmp.status == BH_OK) {  // the file's width and |height|
+      m.original_width = p.bmp.width;
+      m.original_height = p.bmp.height;
     } else if (p.fmt == kFmtWebp && p.webp.status == WH_OK) {
       m.original_width = p.webp.width;
       m.original_height = p.webp.height;
@@ -353,6 +357,7 @@ dg_status Context::pool_tables(Batch &b) {
     // (planning may run on pool threads; dg_last_error is the caller's)
     if (p.status == DG_ERR_UNSUPPORTED && p.fmt == kFmtPng && p.png.depth == 16) set_error(p.png.why);
     if (p.status && p.fmt == kFmtGif && p.gif.why[0]) set_error(p.gif.why);
+    if (p.status && p.fmt == kFmtBmp && p.bmp.why[0]) set_error(p.bmp.why);
     if (p.status && p.fmt == kFmtWebp && p.webp.why[0]) set_error(p.webp.why);
     if (p.status && p.fmt == kFmtVp8 && p.vp8.why[0]) set_error(p.vp8.why);
     if (p.status || p.fmt != kFmtJpeg) continue;
@@ -454,6 +459,8 @@ void Context::layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl) {
       layout_png(a, i, b, bl, d, o);
     else if (p.fmt == kFmtGif)
       layout_gif(a, i, b, bl, d, o);
+    else if (p.fmt == kFmtBmp)
+      layout_bmp(a, i, b, bl, d, o);
     else if (p.fmt == kFmtWebp)
       layout_webp(a, i, b, bl, d, o);
     else if (p.fmt == kFmtVp8)
@@ -668,6 +675,35 @@ void Context::layout_gif(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, 
   b.blob.insert(b.blob.end(), &g.pal[0][0], &g.pal[0][0] + 1024);
   if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
   b.any_gif = true;
+}
+
+// A BMP (option "bmp"): the pixel array or the RLE stream is read in place; an RLE file's index plane and
+// the Rgb8 / Rgba8 pixels, which then are what an 8-bit PNG's pixels are.
+void Context::layout_bmp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
+  const BmpHeader &g = b.plans[i].bmp;
+  d.fmt = kFmtBmp;
+  d.width = g.width;
+  d.height = g.height;
+  d.dec_c = (uint32_t)g.out_c;
+  BmpDesc &bd = d.bmp;
+  bd.bits = (uint32_t)g.bits;
+  bd.rle = g.compression == BMP_RLE8 ? 1u : g.compression == BMP_RLE4 ? 2u : 0u;
+  bd.stride = g.stride;
+  bd.top_down = (uint32_t)g.top_down;
+  bd.npal = (uint32_t)g.npal;
+  bd.pos = (uint32_t)g.pos[0] | ((uint32_t)g.pos[1] << 8) | ((uint32_t)g.pos[2] << 16) | ((g.pos[3] < 0 ? 4u : (uint32_t)g.pos[3]) << 24);
+  bd.data_len = (uint32_t)g.data_len;
+  if (bd.rle) o.raw = bl.L.take((size_t)g.width * g.height + 64, 256);
+  d.pix_stride = (uint32_t)align_up((size_t)g.width * d.dec_c, 16);
+  o.pix = bl.late().take((size_t)d.pix_stride * g.height);
+  o.late |= bl.alias ? 2u : 0u;
+  if (g.bits <= 8) {
+    while (b.blob.size() % 4) b.blob.push_back(0);  // k_bmp_expand loads whole entries
+    o.pal = b.blob.size();
+    b.blob.insert(b.blob.end(), &g.pal[0][0], &g.pal[0][0] + 1024);
+  }
+  if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
+  b.any_bmp = true;
 }
 
 // A lossless WebP (option "webp"), sized from the header alone: the coded bytes are read in place; the work
@@ -1206,8 +1242,10 @@ void Context::layout_batch_regions(Batch &b, BatchLayout &bl) {
       }
     b.words_off = L.take(tot, 256);
     b.words_bytes = tot;
-    for (Offs &o : bl.offs)
-      if (o.tout) o.ewords += b.words_off;
+    // (by the descriptor, not by o.tout: a batch's first image may hold tout at offset 0 of the arena, as a
+    // BMP without an index plane does)
+    for (size_t k = 0; k < bl.offs.size() && k < b.descs.size(); k++)
+      if (b.descs[k].enc.active) bl.offs[k].ewords += b.words_off;
     EncTables et;
     jpeg_enc_tables(et);
     while (b.blob.size() % 16) b.blob.push_back(0);
@@ -1329,6 +1367,15 @@ static void patch_gif(const GifHeader &g, const uint8_t *src, char *S, const Off
   }
 }
 
+static void patch_bmp(const BmpHeader &g, const uint8_t *src, char *S, const Offs &o, ImageDesc &d) {
+  BmpDesc &bd = d.bmp;
+  d.pix = (uint64_t)(uintptr_t)(S + o.pix);
+  bd.src = (uint64_t)(uintptr_t)(src + g.data_off);
+  bd.src_end = bd.src + g.data_len;
+  if (bd.rle) bd.idx = (uint64_t)(uintptr_t)(S + o.raw);
+  bd.pal = g.bits <= 8 ? o.pal + 1 : 0;  // blob offset + 1, made absolute with the meta buffer
+}
+
 static void patch_webp(const WebpHeader &g, const uint8_t *src, char *S, const Offs &o, ImageDesc &d) {
   Vp8lDesc &vd = d.vp8l;
   vd.work = (uint64_t)(uintptr_t)(S + o.raw);
@@ -1380,6 +1427,8 @@ void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const Bat
       patch_png(b.plans[i].png, src, S, o, d, b);
     else if (d.fmt == kFmtGif)
       patch_gif(b.plans[i].gif, src, S, o, d, b);
+    else if (d.fmt == kFmtBmp)
+      patch_bmp(b.plans[i].bmp, src, S, o, d);
     else if (d.fmt == kFmtWebp)
       patch_webp(b.plans[i].webp, src, S, o, d);
     else if (d.fmt == kFmtVp8)
@@ -1642,6 +1691,9 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
   } else if (d.fmt == kFmtWebp) {
     b.lists[L_VP8L].push_back({I, 0});
     for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_VP8L_STORE].push_back({I, it});
+  } else if (d.fmt == kFmtBmp) {
+    if (d.bmp.rle) b.lists[L_BMP_RLE].push_back({I, 0});
+    for (uint32_t it = 0; it < bmp_row_groups(d.width) * d.height; it += 64) b.lists[L_BMP_EXPAND].push_back({I, it});
   } else if (d.fmt == kFmtGif) {
     b.lists[L_GIF_LZW].push_back({I, 0});
     for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_GIF_EXPAND].push_back({I, it});
@@ -1766,6 +1818,7 @@ dg_status Context::stage_and_upload(const SubmitArgs &a, Slot &sl, Batch &b, con
   if (st) return st;
   for (ImageDesc &d : b.descs) {
     if (d.fmt == kFmtPng && d.png.pal) d.png.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.png.pal - 1);
+    if (d.fmt == kFmtBmp && d.bmp.pal) d.bmp.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.bmp.pal - 1);
     if (d.fmt == kFmtGif) d.gif.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.gif.pal - 1);
     if (d.enc.active) {
       d.enc.hdr = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.enc.hdr - 1);

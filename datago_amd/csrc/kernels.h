@@ -119,6 +119,10 @@ void launch_png_expand16(hipStream_t st, const ImageDesc *imgs, const WgItem *li
 void launch_gif_gather(hipStream_t st, const GatherJob *jobs, const WgItem *list, uint32_t nwg);
 void launch_gif_lzw(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_gif_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// BMP (dg_bmp.hip, option "bmp"): rle = one 64-thread workgroup (one wave) per RLE8 / RLE4 image, expand = 64
+// groups of four pixels of a row (256 outputs) per 64-thread workgroup
+void launch_bmp_rle(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_bmp_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // lossless WebP (dg_vp8l.hip, option "webp"): decode and inverse = one 64-thread workgroup (one wave) per
 // image, store = 256 pixels per workgroup
 void launch_vp8l_decode(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);

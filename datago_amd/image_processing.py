@@ -89,8 +89,9 @@ class ARAwareTransform:
 
     def __init__(self, cfg: ImageTransformConfig, device: int = 0, png16: bool = False, resize16: bool = False,
                  penc_dynamic: bool = False, penc16: bool = False, jenc_optimize: bool = False, gif: bool = False,
-                 webp: bool = False, webp_lossy: bool = False, webp_alpha: bool = False):
+                 webp: bool = False, webp_lossy: bool = False, webp_alpha: bool = False, bmp: bool = False):
         self.cfg = cfg
+        self.bmp = bmp  # context option "bmp": a Windows bitmap decodes on the GPU as RGB8 / RGBA8
         self.webp_alpha = webp_alpha  # context option "webp_alpha": with webp_lossy, a lossy WebP with alpha decodes on the GPU as RGBA8
         self.webp_lossy = webp_lossy  # context option "webp_lossy": a lossy WebP without alpha decodes on the GPU as RGB8
         self.webp = webp  # context option "webp": a lossless WebP decodes on the GPU as RGB8 / RGBA8
@@ -126,7 +127,7 @@ class ARAwareTransform:
                                           png16=self.png16, resize16=self.resize16, penc16=self.penc16,
                                           penc_dynamic=self.penc_dynamic, jenc_optimize=self.jenc_optimize,
                                           gif=self.gif, webp=self.webp, webp_lossy=self.webp_lossy,
-                                          webp_alpha=self.webp_alpha)
+                                          webp_alpha=self.webp_alpha, bmp=self.bmp)
         return self._ctx[key]
 
 

@@ -63,7 +63,7 @@ typedef enum dg_status {
 } dg_status;
 
 /* Image formats reported by dg_probe. */
-enum { DG_FMT_UNKNOWN = 0, DG_FMT_JPEG = 1, DG_FMT_PNG = 2, DG_FMT_GIF = 3, DG_FMT_WEBP = 4 };
+enum { DG_FMT_UNKNOWN = 0, DG_FMT_JPEG = 1, DG_FMT_PNG = 2, DG_FMT_GIF = 3, DG_FMT_WEBP = 4, DG_FMT_BMP = 5 };
 
 /* Mirrors ImageTransformConfig (image_processing.rs:43-70) + ImageEncoding (:24-30). */
 typedef struct dg_image_config {
@@ -112,11 +112,11 @@ typedef struct dg_probe_info {
   int32_t format;         /* DG_FMT_* */
   uint32_t width, height;
   int32_t components;     /* 1 (L8) or 3 (RGB8) for JPEG; 4 (Rgba8 on the logical screen) for GIF;
-                             3 (Rgb8) or 4 (Rgba8) for a lossless or extended WebP */
+                             3 (Rgb8) or 4 (Rgba8) for a lossless or extended WebP and for a BMP */
   int32_t bit_depth;      /* bits per channel (8; 16 for a 16-bit PNG) */
   int32_t h_samp[4], v_samp[4];
   int32_t progressive, arithmetic, precision, restart_interval;
-  int32_t gpu_supported;  /* 1 if dg_submit would decode it on the GPU with the default options (0 for a GIF or a WebP) */
+  int32_t gpu_supported;  /* 1 if dg_submit would decode it on the GPU with the default options (0 for a GIF, a WebP or a BMP) */
 } dg_probe_info;
 
 /* Header-only: lets the caller compute the bucket and size the output before
@@ -338,6 +338,26 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 screen over 512 MiB of Rgba8 or over the GPU path's 32-bit working set.  DG_ERR_CORRUPT:
  *                 a file ending inside a header, table, extension or sub-block chain, no image
  *                 descriptor, no colour table.  Any other value: DG_ERR_INVALID
+ *   "bmp"         1 = decode Windows bitmaps on the GPU (default 0: DG_ERR_CORRUPT from every entry point,
+ *                 like any format the library does not know; dg_probe names a BMP either way, DG_FMT_BMP
+ *                 with gpu_supported 0).  The output is what image 0.25's BmpDecoder returns for
+ *                 load_from_memory, top row first, for the files it and Pillow decode to the same bytes:
+ *                 Rgb8 for 1 / 4 / 8-bit palette files (BI_RGB, and bottom-up BI_RLE8 / BI_RLE4 streams
+ *                 that write every pixel once in row order, without delta codes), 24-bit files and 32-bit
+ *                 BI_RGB under a 40-byte header; Rgb8 or, with an alpha mask, non-premultiplied Rgba8
+ *                 for 32-bit BI_BITFIELDS with byte-aligned masks.  Core (12), INFO (40), V4 and V5
+ *                 headers, bfOffBits honoured.  From there the image behaves as an 8-bit RGB / RGBA PNG
+ *                 of the same pixels (original_* = the file's width and |height|).  DG_ERR_UNSUPPORTED,
+ *                 each with a dg_last_error text of its own: 16 or 2 bits per pixel, 32-bit BI_RGB under
+ *                 a V4 / V5 header, other mask sets, header sizes 52 / 56 / 64, BI_JPEG / BI_PNG and any
+ *                 other compression, top-down RLE, RLE on a mismatched depth, planes not 1, a colour
+ *                 table larger than the depth allows, a zero dimension, an image over 512 MiB or over
+ *                 the GPU path's 32-bit working set, and, found while decoding: an RLE run or absolute
+ *                 block that passes its row's end, a delta / early end-of-line / early end-of-bitmap,
+ *                 RLE data that ends early, a pixel index past the colour table.  DG_ERR_CORRUPT: a file
+ *                 ending inside a header, the masks or the colour table, bfOffBits inside the headers or
+ *                 past the file, an uncompressed pixel array cut short, an unknown info-header size.
+ *                 Any other value: DG_ERR_INVALID
  *   "webp"        1 = decode still lossless WebP files on the GPU: a RIFF/WEBP file whose image data is a
  *                 VP8L chunk, alone (simple file) or behind VP8X with ICCP / EXIF / XMP / unknown chunks
  *                 skipped (default 0: DG_ERR_CORRUPT from every entry point, like any format the library
