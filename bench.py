@@ -991,15 +991,13 @@ def main() -> int:
             res = ctx.decode_batch([pool[i] for i in idx], [forced_pool[i] for i in idx])
             e2e_px += sum(dims[i][0] * dims[i][1] for i, r in zip(idx, res) if r[0] == 0)
         e2e_sync = e2e_px / (time.perf_counter() - t1) / 1e6
-        # the loader's steady state: a reused, page-locked output pool (dg_host_register), batches
+        # the loader's steady state: a reused, page-locked output pool (dg_host_alloc), batches
         # pipelined (batch k + inflight - 1 submitted before batch k is waited on); outputs DMA'd from
         # HBM straight into the pool
         n_e2e = max(a.e2e_steps, 2 * a.inflight)
         arenas = []
         for _ in range(a.inflight):
-            ar = np.zeros(out_cap, np.uint8)
-            ctx.host_register(ar)
-            arenas.append(ar)
+            arenas.append(ctx.host_alloc(out_cap))
         direct0 = ctx.stat("direct_d2h")
 
         def host_submit(k):
@@ -1028,7 +1026,7 @@ def main() -> int:
         e2e_direct = ctx.stat("direct_d2h") - direct0
         e2e_out_gbs = e2e_out / dt_e2e / 1e9
         for ar in arenas:
-            ctx.host_unregister(ar)
+            ctx.host_free(ar)
         # host coded bytes in -> HBM tensors out (the training-loop hand-off: PCIe carries the
         # compressed stream only)
         t1 = time.perf_counter()
@@ -1056,9 +1054,7 @@ def main() -> int:
         fails = [0] * a.one_threads
 
         # one reused, page-locked output buffer per calling thread (the glue's payload buffers)
-        one_bufs = [np.zeros(max(out_bytes), np.uint8) for _ in range(a.one_threads)]
-        for ob_ in one_bufs:
-            ctx.host_register(ob_)
+        one_bufs = [ctx.host_alloc(max(out_bytes)) for _ in range(a.one_threads)]
 
         def one_worker(t):
             while True:
@@ -1080,7 +1076,7 @@ def main() -> int:
             th.join()
         dt1 = time.perf_counter() - t1
         for ob_ in one_bufs:
-            ctx.host_unregister(ob_)
+            ctx.host_free(ob_)
         nb_ = ctx.stat("coalesced_batches") - b0
         one = {"threads": a.one_threads, "images": n_one, "failed": sum(fails),
                "mpix_s": round(sum(done_px) / dt1 / 1e6, 2), "images_per_s": round(n_one / dt1, 1),
@@ -1088,7 +1084,7 @@ def main() -> int:
                "coalesce_max": 64, "coalesce_us": 500, "coalesce_inflight": ctx.stat("coalesce_inflight"),
                "prog_lanes": a.prog_lanes,
                "note": "host JPEG bytes in -> host RGB out per call (PCIe both ways) into a reused page-locked "
-                       "buffer per thread (dg_host_register), like e2e_host_mpix_s"}
+                       "buffer per thread (dg_host_alloc), like e2e_host_mpix_s"}
         # the same calls from native threads (tools/one_bench, linked to the library): the Rust glue's
         # tokio workers are native; Python threads also contend for the interpreter lock between calls
         native = os.path.join(ROOT, "tools", "one_bench")
@@ -1284,7 +1280,7 @@ def main() -> int:
             "rank_cpus": (f"{len(pinned)} CPUs per rank, disjoint contiguous shares of the job's affinity set"
                           if pinned else "unpinned"),
             "e2e_host_mpix_s": round(e2e, 2) if e2e else None,
-            "e2e_host_detail": ({"note": "host JPEG bytes in -> host RGB out, a dg_host_register'ed output pool "
+            "e2e_host_detail": ({"note": "host JPEG bytes in -> host RGB out, a dg_host_alloc'ed output pool "
                                          "reused, batches pipelined; outputs DMA'd from HBM into the pool",
                                  "outputs_direct_dma": e2e_direct, "output_GBs": round(e2e_out_gbs, 2),
                                  "d2h_pinned_GBs": round(d2h, 2) if d2h else None,

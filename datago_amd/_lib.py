@@ -41,6 +41,7 @@ EXPORTS = [
     "dg_memcpy_h2d", "dg_memcpy_d2h", "dg_synchronize", "dg_last_batch_timings",
     "dg_ctx_set_option", "dg_ctx_get_stat", "dg_last_error", "dg_abi_version", "dg_sample_align",
     "dg_wds_index", "dg_wds_key_hash", "dg_host_register", "dg_host_unregister",
+    "dg_host_alloc", "dg_host_free",
 ]
 
 
@@ -118,6 +119,8 @@ def load() -> ctypes.CDLL:
     L.dg_synchronize.argtypes = [vp]
     L.dg_host_register.argtypes = [vp, vp, sz]
     L.dg_host_unregister.argtypes = [vp, vp]
+    L.dg_host_alloc.argtypes = [vp, sz, ctypes.POINTER(vp)]
+    L.dg_host_free.argtypes = [vp, vp]
     L.dg_last_batch_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), i32]
     L.dg_ctx_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_int64]
     L.dg_ctx_get_stat.argtypes = [vp, ctypes.c_char_p]
@@ -573,3 +576,14 @@ class Context:
 
     def host_unregister(self, arr: np.ndarray) -> None:
         _check(load().dg_host_unregister(self._h, arr.ctypes.data))
+
+    def host_alloc(self, nbytes: int) -> np.ndarray:
+        """dg_host_alloc: a zeroed, page-locked uint8 array (a reused output
+        array or arena where existing memory cannot be registered).  The
+        array and its views are invalid after host_free(arr)."""
+        p = ctypes.c_void_p()
+        _check(load().dg_host_alloc(self._h, nbytes, ctypes.byref(p)))
+        return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), (nbytes,))
+
+    def host_free(self, arr: np.ndarray) -> None:
+        _check(load().dg_host_free(self._h, arr.ctypes.data))

@@ -426,6 +426,16 @@ dg_status dg_host_unregister(dg_ctx *ctx, void *ptr) {
   DG_USE(ctx, DG_ERR_INVALID);
   return ctx->c->host_unregister(ptr);
 }
+dg_status dg_host_alloc(dg_ctx *ctx, size_t bytes, void **ptr) {
+  if (!ptr || !bytes) return DG_ERR_INVALID;
+  DG_USE(ctx, DG_ERR_INVALID);
+  return ctx->c->host_alloc(bytes, ptr);
+}
+dg_status dg_host_free(dg_ctx *ctx, void *ptr) {
+  if (!ptr) return DG_ERR_INVALID;
+  DG_USE(ctx, DG_ERR_INVALID);
+  return ctx->c->host_free(ptr);
+}
 dg_status dg_synchronize(dg_ctx *ctx) {
   DG_USE(ctx, DG_ERR_INVALID);
   hipSetDevice(ctx->c->device());

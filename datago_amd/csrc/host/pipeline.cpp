@@ -219,8 +219,10 @@ dg_status Context::make_streams(int first, int count, int mode, int cus, int sid
 
 dg_status Context::host_register(void *ptr, size_t bytes) {
   HIPCHK(hipSetDevice(device_));
-  if (hipHostRegister(ptr, bytes, hipHostRegisterDefault) != hipSuccess) {
-    set_error("hipHostRegister failed");
+  const hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterDefault);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();  // reported here: the next launch's check must not meet it
+    set_error(std::string("hipHostRegister failed: ") + hipGetErrorString(e));
     return DG_ERR_DEVICE;
   }
   std::lock_guard<std::mutex> lk(reg_mu_);
@@ -228,7 +230,8 @@ dg_status Context::host_register(void *ptr, size_t bytes) {
   return DG_OK;
 }
 
-dg_status Context::host_unregister(void *ptr) {
+// Forget the range that starts at ptr and wait for copies into it.
+void Context::host_forget(void *ptr) {
   {
     std::lock_guard<std::mutex> lk(reg_mu_);
     for (size_t i = 0; i < registered_.size(); i++)
@@ -238,8 +241,40 @@ dg_status Context::host_unregister(void *ptr) {
       }
   }
   sync_all();  // no copy into the range may still be in flight
+}
+
+dg_status Context::host_unregister(void *ptr) {
+  host_forget(ptr);
   HIPCHK(hipSetDevice(device_));
-  return hipHostUnregister(ptr) == hipSuccess ? DG_OK : DG_ERR_INVALID;
+  if (hipHostUnregister(ptr) != hipSuccess) {
+    (void)hipGetLastError();  // as in host_register
+    return DG_ERR_INVALID;
+  }
+  return DG_OK;
+}
+
+dg_status Context::host_alloc(size_t bytes, void **ptr) {
+  HIPCHK(hipSetDevice(device_));
+  if (hipHostMalloc(ptr, bytes, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    *ptr = nullptr;
+    set_error("hipHostMalloc failed");
+    return DG_ERR_OOM;
+  }
+  memset(*ptr, 0, bytes);
+  std::lock_guard<std::mutex> lk(reg_mu_);
+  registered_.push_back({(uintptr_t)*ptr, bytes});
+  return DG_OK;
+}
+
+dg_status Context::host_free(void *ptr) {
+  host_forget(ptr);
+  HIPCHK(hipSetDevice(device_));
+  if (hipHostFree(ptr) != hipSuccess) {
+    (void)hipGetLastError();
+    return DG_ERR_INVALID;
+  }
+  return DG_OK;
 }
 
 bool Context::host_pinned(const void *ptr, size_t bytes) {

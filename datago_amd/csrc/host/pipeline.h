@@ -274,6 +274,9 @@ class Context {
   dg_status sync_all();  // every stream of the context
   dg_status host_register(void *ptr, size_t bytes);
   dg_status host_unregister(void *ptr);
+  dg_status host_alloc(size_t bytes, void **ptr);
+  dg_status host_free(void *ptr);
+  void host_forget(void *ptr);
   bool host_pinned(const void *ptr, size_t bytes);  // inside a registered range, or runtime-pinned memory
   dg_status set_option(const std::string &k, int64_t v);
   int64_t get_stat(const std::string &k);
@@ -504,7 +507,7 @@ class Context {
   int64_t stat_prog_items_ = 0, stat_prog_chains_ = 0;  // pipelined progressive launches: work items, chains
   std::vector<float> last_ms_;
   std::mutex reg_mu_;
-  std::vector<std::pair<uintptr_t, size_t>> registered_;  // dg_host_register ranges
+  std::vector<std::pair<uintptr_t, size_t>> registered_;  // dg_host_register and dg_host_alloc ranges
   int64_t stat_direct_d2h_ = 0;                           // outputs copied straight into caller memory
 };
 

@@ -230,9 +230,19 @@ dg_status dg_synchronize(dg_ctx *ctx);
  * range (or in memory the HIP runtime already pins) are copied by DMA straight
  * from HBM into it -- no pinned staging buffer, no host memcpy, no first-touch
  * page faults.  Meant for a reused output-buffer pool (the Rust glue's payload
- * arena); registering costs about as much as touching the pages once. */
+ * arena); registering costs about as much as touching the pages once.  Where
+ * the runtime cannot page-lock existing memory (some virtual machines),
+ * dg_host_register returns DG_ERR_DEVICE and leaves the context usable: take
+ * the pool from dg_host_alloc there. */
 dg_status dg_host_register(dg_ctx *ctx, void *ptr, size_t bytes);
 dg_status dg_host_unregister(dg_ctx *ctx, void *ptr);
+
+/* A page-locked host range allocated by the library (hipHostMalloc), zeroed,
+ * for callers without a GPU runtime of their own: outputs into it take the
+ * same direct path as into a registered range.  dg_host_free waits for copies
+ * in flight; free every range before dg_ctx_destroy. */
+dg_status dg_host_alloc(dg_ctx *ctx, size_t bytes, void **ptr);
+dg_status dg_host_free(dg_ctx *ctx, void *ptr);
 
 /* Per-kernel timing of the last completed batch (HIP events on the context's
  * stream).  names[i] points to static strings; returns the number of stages. */

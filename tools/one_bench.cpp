@@ -2,7 +2,7 @@
 // (the Rust glue's tokio workers call the library from native threads, one
 // image per call; bench.py's Python threads also contend for the interpreter
 // lock between calls).  Host JPEG bytes in -> host RGB out, one reused
-// page-locked output buffer per thread (dg_host_register), as in bench.py's
+// page-locked output buffer per thread (dg_host_alloc), as in bench.py's
 // e2e_decode_one.  Prints one JSON object.
 //
 //   one_bench POOL THREADS IMAGES SIZE RATIO SEM [key=value context options...]
@@ -58,16 +58,16 @@ int main(int argc, char **argv) {
     uint64_t nb = 0;
     if (dg_output_size(ctx, d.data(), d.size(), -1, &nb) == DG_OK && nb > cap) cap = nb;
   }
-  std::vector<std::vector<uint8_t>> bufs(threads, std::vector<uint8_t>(cap));
+  std::vector<uint8_t *> bufs(threads, nullptr);
   for (auto &b : bufs)
-    if (dg_host_register(ctx, b.data(), b.size()) != DG_OK) return 3;
+    if (dg_host_alloc(ctx, cap, (void **)&b) != DG_OK) return 3;
   std::atomic<int> next{0};
   std::atomic<int64_t> px{0}, fails{0};
   auto work = [&](int t, int count) {
     for (int i; (i = next.fetch_add(1)) < count;) {
       const auto &d = pool[(size_t)i % n];
       dg_payload_meta m;
-      if (dg_decode_one(ctx, d.data(), d.size(), -1, bufs[t].data(), cap, &m) == DG_OK)
+      if (dg_decode_one(ctx, d.data(), d.size(), -1, bufs[t], cap, &m) == DG_OK)
         px += (int64_t)m.original_width * m.original_height;
       else
         fails++;
@@ -96,7 +96,7 @@ int main(int argc, char **argv) {
          "\"gpu_batches\": %lld, \"mean_images_per_batch\": %.1f}\n",
          threads, images, (long long)fails.load(), (double)px.load() / s / 1e6, images / s, (long long)nb,
          nb ? (double)ni / (double)nb : 0.0);
-  for (auto &b : bufs) dg_host_unregister(ctx, b.data());
+  for (auto &b : bufs) dg_host_free(ctx, b);
   dg_ctx_destroy(ctx);
   return 0;
 }
