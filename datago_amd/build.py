@@ -30,6 +30,7 @@ SOURCES = [
     ("dg_resize16.hip", True),
     ("dg_gif.hip", True),
     ("dg_bmp.hip", True),
+    ("dg_tiff.hip", True),
     ("dg_vp8l.hip", True),
     ("dg_vp8.hip", True),
     ("dg_alph.hip", True),
@@ -38,6 +39,7 @@ SOURCES = [
     ("host/png_header.cpp", False),
     ("host/gif_header.cpp", False),
     ("host/bmp_header.cpp", False),
+    ("host/tiff_header.cpp", False),
     ("host/webp_header.cpp", False),
     ("host/options.cpp", False),
     ("host/pipeline.cpp", False),

@@ -176,7 +176,7 @@ constexpr uint32_t kHBandsDefault = 16;  // default ResizePass::bands (8 -> 16: 
 constexpr int kStages = 4;  // R1.H, R1.V, R2.H, R2.V
 
 // ---- PNG (ImageDesc::fmt == kFmtPng)
-constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1, kFmtGif = 2, kFmtWebp = 3, kFmtVp8 = 4, kFmtBmp = 5;
+constexpr uint32_t kFmtJpeg = 0, kFmtPng = 1, kFmtGif = 2, kFmtWebp = 3, kFmtVp8 = 4, kFmtBmp = 5, kFmtTiff = 6;
 // IDAT payloads are gathered into one contiguous zlib stream (k_png_gather),
 // inflated into filtered scanlines (k_png_inflate, one wave per image),
 // unfiltered (k_png_unfilter, one wave per 64-row band on a diagonal
@@ -250,6 +250,36 @@ constexpr uint32_t kBmpFailRow = 1;      // a run or absolute block that passes 
 constexpr uint32_t kBmpFailDelta = 2;    // a delta, an early end-of-line or an end-of-bitmap with pixels unwritten
 constexpr uint32_t kBmpFailShort = 3;    // the data ends before the last pixel
 constexpr uint32_t kBmpFailPalette = 4;  // an index at or past the colour table's size
+
+// ---- TIFF (ImageDesc::fmt == kFmtTiff, option "tiff"): an 8-bit chunky TIFF as L8 / La8 / Rgb8 / Rgba8.
+// The file is cut into segments (strips or tiles), each a coded stream of its own: k_tiff_lzw and
+// k_tiff_packbits give one wave to every (image, segment) and write the segment's bytes into the
+// decoded arena; k_tiff_expand reads them, or for compression 1 the file's own bytes, undoes predictor 2,
+// inverts WhiteIsZero and places rows and tiles in the pixel plane (dg_tiff.h, dg_tiff.hip).  A
+// segment that does not decode sets ImageDesc::status and TiffDesc::fail names it.
+struct TiffSeg {
+  uint32_t off;     // the coded bytes: offset in the file (any byte alignment) ...
+  uint32_t nbytes;  // ... and count
+  uint32_t dec;     // bytes the segment decodes to: rows x row bytes (a tile: always the whole tile)
+  uint32_t dst;     // offset of those bytes in the decoded arena (a multiple of 16)
+};
+struct TiffDesc {
+  uint64_t file;      // the file's first byte
+  uint64_t segs;      // TiffSeg[nseg] (device)
+  uint64_t dec;       // the decoded arena (compression 5 / 32773)
+  uint32_t nseg;
+  uint32_t comp;      // 1, 5 (LZW) or 32773 (PackBits)
+  uint32_t pred;      // 1 or 2
+  uint32_t invert;    // WhiteIsZero
+  uint32_t spp;       // samples per pixel, 1 .. 4
+  uint32_t seg_w;     // pixels per segment row: the tile width, or the image width for strips
+  uint32_t seg_h;     // rows per segment: the tile length or RowsPerStrip
+  uint32_t across;    // segments side by side: tiles per row, 1 for strips
+  uint32_t fail;      // kTiffFail*: written by k_tiff_lzw / k_tiff_packbits
+};
+constexpr uint32_t kTiffFailCode = 1;   // an LZW code above the next free one
+constexpr uint32_t kTiffFailShort = 2;  // a segment ends (or its end code comes) before its last byte
+constexpr uint32_t kTiffFailFull = 3;   // an LZW table that stays full for over kTiffFullCodes codes (libtiff refuses it)
 
 // ---- lossless WebP (ImageDesc::fmt == kFmtWebp, option "webp"): a VP8L chunk as Rgb8 / Rgba8.
 // k_vp8l_decode (one wave per image, dg_vp8l.h) reads the bitstream after the 5-byte header in place:
@@ -537,7 +567,7 @@ struct ImageDesc {
   uint32_t final_src_c;
   uint32_t color_fused;     // 1: pass[0] converts colour itself, pix is never written
   // ---- format, PNG, alpha handling, final conversion
-  uint32_t fmt;             // kFmtJpeg / kFmtPng / kFmtGif / kFmtWebp / kFmtVp8 / kFmtBmp
+  uint32_t fmt;             // kFmtJpeg / kFmtPng / kFmtGif / kFmtWebp / kFmtVp8 / kFmtBmp / kFmtTiff
   uint32_t prog;            // progressive JPEG: scans decoded by k_prog_scan (0: sequential)
   uint32_t crec;            // bit c: component c's plane holds chroma records (dg_plane.h; option "chroma_rec")
   uint32_t copy_mode;       // k_copy: 0 same channels, 1 L->RGB, 2 RGBA->RGB blend over gray,
@@ -552,6 +582,7 @@ struct ImageDesc {
     Vp8lDesc vp8l;          // fmt == kFmtWebp
     Vp8Desc vp8;            // fmt == kFmtVp8
     BmpDesc bmp;            // fmt == kFmtBmp
+    TiffDesc tiff;          // fmt == kFmtTiff
   };
   AlphaOp aop[kAlphaPoints];
   EncDesc enc;

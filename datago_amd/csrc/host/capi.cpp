@@ -245,6 +245,22 @@ dg_status dg_probe(const uint8_t *bytes, size_t len, dg_probe_info *out) {
     }
     return DG_OK;
   }
+  if (dg::is_tiff(bytes, len)) {
+    dg::TiffHeader h;
+    dg::parse_tiff_header(bytes, len, h);
+    out->format = DG_FMT_TIFF;
+    out->width = h.width;
+    out->height = h.height;
+    out->components = h.out_c;  // 1 (L8), 2 (La8), 3 (Rgb8), 4 (Rgba8); 0 for a form the library does not decode
+    out->bit_depth = 8;
+    out->precision = 8;
+    out->gpu_supported = 0;  // the default options (option "tiff" decodes it)
+    if (h.status == dg::TH_CORRUPT) {
+      dg::set_error(h.why);
+      return DG_ERR_CORRUPT;
+    }
+    return DG_OK;
+  }
   if (dg::is_webp(bytes, len)) {  // lossless or extended; a simple lossy file stays an unknown format
     dg::WebpHeader h;
     dg::parse_webp_header(bytes, len, h);

@@ -240,7 +240,8 @@ const int kNumOptions = (int)(sizeof(kOptionTable) / sizeof(kOptionTable[0]));
 // defaults one by one: that test reads kOptionTable alone and holds it to
 // exactly that list, so a later option stands here, with a test of its own
 // (tests/test_vp8_cpu.py for "webp_lossy", tests/test_alph_cpu.py for
-// "webp_alpha", tests/test_bmp_cpu.py for "bmp").  find_option looks through both,
+// "webp_alpha", tests/test_bmp_cpu.py for "bmp", tests/test_tiff_cpu.py for
+// "tiff").  find_option looks through both,
 // so to dg_ctx_set_option the two tables are one.
 const OptRow kOptionTableAdded[] = {
     // Still lossy WebP files (a `VP8 ` image chunk, simple or behind VP8X, no
@@ -284,6 +285,18 @@ const OptRow kOptionTableAdded[] = {
     // text.  dg_probe names a BMP either way and keeps describing the default
     // options.
     STRICT("bmp", bmp),
+    // TIFF files on the GPU (default off: DG_ERR_CORRUPT like any format the
+    // library does not know).  1: plan_image takes a classic TIFF's first IFD:
+    // 8-bit chunky gray, gray + alpha, RGB and RGBA, uncompressed, PackBits or
+    // LZW, predictor 1 or 2, in strips or tiles.  k_tiff_lzw / k_tiff_packbits
+    // decode one segment per wave, k_tiff_expand places rows and tiles, undoes
+    // the predictor and inverts WhiteIsZero (dg_tiff.hip): what image 0.25's
+    // TiffDecoder returns for load_from_memory, for the files it and libtiff
+    // decode alike.  From there it is an 8-bit PNG's pixels.  Every other form
+    // comes back DG_ERR_UNSUPPORTED with a dg_last_error text, a broken IFD or
+    // segment DG_ERR_CORRUPT.  dg_probe names a TIFF either way and keeps
+    // describing the default options.
+    STRICT("tiff", tiff),
 };
 const int kNumOptionsAdded = (int)(sizeof(kOptionTableAdded) / sizeof(kOptionTableAdded[0]));
 

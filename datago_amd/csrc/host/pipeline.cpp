@@ -1110,6 +1110,24 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     W = p.bmp.width;
     H = p.bmp.height;
     C = (uint32_t)p.bmp.out_c;
+  } else if (opt_.tiff && is_tiff(h, len)) {  // option "tiff"
+    p.fmt = kFmtTiff;
+    parse_tiff_header(h, len, p.tiff);
+    if (p.tiff.status != TH_OK) {
+      p.status = p.tiff.status == TH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
+      return DG_OK;
+    }
+    // the limits of the BMP path: the pixel buffer and the file stay 32-bit addressable (the decoded arena
+    // is held under 2^31 by the header walk)
+    if ((uint64_t)p.tiff.width * p.tiff.height * 4ull >= (1ull << 31) || len >= (1ull << 28)) {
+      p.tiff.status = TH_UNSUPPORTED;
+      p.tiff.why = "TIFF: image too large for the GPU path";
+      p.status = DG_ERR_UNSUPPORTED;
+      return DG_OK;
+    }
+    W = p.tiff.width;
+    H = p.tiff.height;
+    C = (uint32_t)p.tiff.out_c;
   } else if (opt_.webp_lossy && is_webp_lossy(h, len) && (parse_webp_lossy(h, len, p.vp8, opt_.webp_alpha), p.vp8.claim)) {
     // option "webp_lossy": a file whose image chunk is VP8L is not claimed and goes on to "webp" below
     p.fmt = kFmtVp8;
@@ -1248,6 +1266,7 @@ dg_status Context::output_size(const uint8_t *bytes, size_t len, int32_t forced,
     set_error(p.fmt == kFmtPng    ? p.png.why
               : p.fmt == kFmtGif  ? p.gif.why
               : p.fmt == kFmtBmp  ? p.bmp.why
+              : p.fmt == kFmtTiff ? p.tiff.why
               : p.fmt == kFmtWebp ? p.webp.why
               : p.fmt == kFmtVp8  ? p.vp8.why
                                   : (p.hdr.why ? p.hdr.why : "unsupported"));
@@ -1494,6 +1513,10 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     launch_gif_lzw(sl.st, dm, lst(L_GIF_LZW), cnt(L_GIF_LZW));
   }
   if (!from_fix && b.any_bmp) launch_bmp_rle(sl.st, dm, lst(L_BMP_RLE), cnt(L_BMP_RLE));  // BMP: RLE stream -> index plane
+  if (!from_fix && b.any_tiff) {  // TIFF: every coded segment -> its bytes in the decoded arena
+    launch_tiff_lzw(sl.st, dm, lst(L_TIFF_LZW), cnt(L_TIFF_LZW));
+    launch_tiff_packbits(sl.st, dm, lst(L_TIFF_PACKBITS), cnt(L_TIFF_PACKBITS));
+  }
   if (!from_fix && b.any_webp) {  // lossless WebP: bitstream -> ARGB plane -> inverse transforms
     launch_vp8l_decode(sl.st, dm, lst(L_VP8L), cnt(L_VP8L));
     launch_vp8l_inverse(sl.st, dm, lst(L_VP8L), cnt(L_VP8L));
@@ -1508,6 +1531,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   if (next()) return DG_ERR_DEVICE;
   if (!from_fix && b.any_gif) launch_gif_expand(sl.st, dm, lst(L_GIF_EXPAND), cnt(L_GIF_EXPAND));
   if (!from_fix && b.any_bmp) launch_bmp_expand(sl.st, dm, lst(L_BMP_EXPAND), cnt(L_BMP_EXPAND));
+  if (!from_fix && b.any_tiff) launch_tiff_expand(sl.st, dm, lst(L_TIFF_EXPAND), cnt(L_TIFF_EXPAND));
   if (!from_fix && b.any_webp) launch_vp8l_store(sl.st, dm, lst(L_VP8L_STORE), cnt(L_VP8L_STORE));
   if (!from_fix && b.any_vp8) launch_vp8_rgb(sl.st, dm, lst(L_VP8_RGB), cnt(L_VP8_RGB));
   if (!from_fix && b.any_png) {
@@ -1883,6 +1907,13 @@ dg_status Context::finish_body(Slot &sl) {
                 : f == kBmpFailShort   ? "BMP: RLE data ends before the bitmap is complete"
                 : f == kBmpFailPalette ? "BMP: pixel index past the colour table"
                                        : "BMP: decode failed");
+    }
+    if (status && back[b.desc_of[i]].fmt == kFmtTiff) {  // what k_tiff_lzw / k_tiff_packbits met in a segment
+      const uint32_t f = back[b.desc_of[i]].tiff.fail;
+      set_error(f == kTiffFailCode    ? "TIFF: LZW code above the next free code"
+                : f == kTiffFailShort ? "TIFF: a segment's data ends before its last row is complete"
+                : f == kTiffFailFull  ? "TIFF: LZW table stays full without a clear code"
+                                      : "TIFF: decode failed");
     }
     if (status && back[b.desc_of[i]].fmt == kFmtWebp) {  // what k_vp8l_decode met in the stream
       const uint32_t f = back[b.desc_of[i]].vp8l.fail;

@@ -17,6 +17,7 @@
 #include "../dg_entropy.h"
 #include "../dg_bmp.h"
 #include "../dg_gif.h"
+#include "../dg_tiff.h"
 #include "../dg_vp8.h"
 #include "../dg_vp8l.h"
 #include "../dg_jenc_tree.h"
@@ -318,6 +319,9 @@ void Context::plan_images(const SubmitArgs &a, Batch &b) {
     } else if (p.fmt == kFmtBmp && p.bmp.status == BH_OK) {  // the file's width and |height|
       m.original_width = p.bmp.width;
       m.original_height = p.bmp.height;
+    } else if (p.fmt == kFmtTiff && p.tiff.status == TH_OK) {  // ImageWidth and ImageLength
+      m.original_width = p.tiff.width;
+      m.original_height = p.tiff.height;
     } else if (p.fmt == kFmtWebp && p.webp.status == WH_OK) {
       m.original_width = p.webp.width;
       m.original_height = p.webp.height;
@@ -358,6 +362,7 @@ dg_status Context::pool_tables(Batch &b) {
     if (p.status == DG_ERR_UNSUPPORTED && p.fmt == kFmtPng && p.png.depth == 16) set_error(p.png.why);
     if (p.status && p.fmt == kFmtGif && p.gif.why[0]) set_error(p.gif.why);
     if (p.status && p.fmt == kFmtBmp && p.bmp.why[0]) set_error(p.bmp.why);
+    if (p.status && p.fmt == kFmtTiff && p.tiff.why[0]) set_error(p.tiff.why);
     if (p.status && p.fmt == kFmtWebp && p.webp.why[0]) set_error(p.webp.why);
     if (p.status && p.fmt == kFmtVp8 && p.vp8.why[0]) set_error(p.vp8.why);
     if (p.status || p.fmt != kFmtJpeg) continue;
@@ -461,6 +466,8 @@ void Context::layout_images(const SubmitArgs &a, Batch &b, BatchLayout &bl) {
       layout_gif(a, i, b, bl, d, o);
     else if (p.fmt == kFmtBmp)
       layout_bmp(a, i, b, bl, d, o);
+    else if (p.fmt == kFmtTiff)
+      layout_tiff(a, i, b, bl, d, o);
     else if (p.fmt == kFmtWebp)
       layout_webp(a, i, b, bl, d, o);
     else if (p.fmt == kFmtVp8)
@@ -704,6 +711,37 @@ void Context::layout_bmp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, 
   }
   if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
   b.any_bmp = true;
+}
+
+// A TIFF (option "tiff"): the segments are read in place; the decoded arena of a compressed file (every
+// segment's bytes, each slot a multiple of 16), the segment table in the blob and the L8 / La8 / Rgb8 / Rgba8
+// pixels, which then are what an 8-bit PNG's pixels are.
+void Context::layout_tiff(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
+  const TiffHeader &g = b.plans[i].tiff;
+  d.fmt = kFmtTiff;
+  d.width = g.width;
+  d.height = g.height;
+  d.dec_c = (uint32_t)g.out_c;
+  TiffDesc &td = d.tiff;
+  td.nseg = (uint32_t)g.segs.size();
+  td.comp = (uint32_t)g.compression;
+  td.pred = (uint32_t)g.predictor;
+  td.invert = (uint32_t)g.invert;
+  td.spp = (uint32_t)g.out_c;
+  td.seg_w = g.seg_w;
+  td.seg_h = g.seg_h;
+  td.across = g.across;
+  if (g.compression != TIFF_NONE) o.raw = bl.L.take((size_t)g.dec_total + 64, 256);
+  d.pix_stride = (uint32_t)align_up((size_t)g.width * d.dec_c, 16);
+  o.pix = bl.late().take((size_t)d.pix_stride * g.height);
+  o.late |= bl.alias ? 2u : 0u;
+  static_assert(sizeof(TiffSegment) == sizeof(TiffSeg), "the segment table is uploaded as it is");
+  while (b.blob.size() % 16) b.blob.push_back(0);
+  o.pal = b.blob.size();
+  const uint8_t *tab = (const uint8_t *)g.segs.data();
+  b.blob.insert(b.blob.end(), tab, tab + g.segs.size() * sizeof(TiffSegment));
+  if (a.host_io) bl.in_off[i] = bl.IN.take(a.lens[i] + 16, 16);
+  b.any_tiff = true;
 }
 
 // A lossless WebP (option "webp"), sized from the header alone: the coded bytes are read in place; the work
@@ -1376,6 +1414,14 @@ static void patch_bmp(const BmpHeader &g, const uint8_t *src, char *S, const Off
   bd.pal = g.bits <= 8 ? o.pal + 1 : 0;  // blob offset + 1, made absolute with the meta buffer
 }
 
+static void patch_tiff(const TiffHeader &g, const uint8_t *src, char *S, const Offs &o, ImageDesc &d) {
+  TiffDesc &td = d.tiff;
+  d.pix = (uint64_t)(uintptr_t)(S + o.pix);
+  td.file = (uint64_t)(uintptr_t)src;
+  if (g.compression != TIFF_NONE) td.dec = (uint64_t)(uintptr_t)(S + o.raw);
+  td.segs = o.pal + 1;  // blob offset + 1, made absolute with the meta buffer
+}
+
 static void patch_webp(const WebpHeader &g, const uint8_t *src, char *S, const Offs &o, ImageDesc &d) {
   Vp8lDesc &vd = d.vp8l;
   vd.work = (uint64_t)(uintptr_t)(S + o.raw);
@@ -1429,6 +1475,8 @@ void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const Bat
       patch_gif(b.plans[i].gif, src, S, o, d, b);
     else if (d.fmt == kFmtBmp)
       patch_bmp(b.plans[i].bmp, src, S, o, d);
+    else if (d.fmt == kFmtTiff)
+      patch_tiff(b.plans[i].tiff, src, S, o, d);
     else if (d.fmt == kFmtWebp)
       patch_webp(b.plans[i].webp, src, S, o, d);
     else if (d.fmt == kFmtVp8)
@@ -1691,6 +1739,10 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
   } else if (d.fmt == kFmtWebp) {
     b.lists[L_VP8L].push_back({I, 0});
     for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_VP8L_STORE].push_back({I, it});
+  } else if (d.fmt == kFmtTiff) {
+    const ListId dec = d.tiff.comp == TIFF_LZW ? L_TIFF_LZW : L_TIFF_PACKBITS;
+    for (uint32_t sg = 0; d.tiff.comp != TIFF_NONE && sg < d.tiff.nseg; sg++) b.lists[dec].push_back({I, sg});
+    for (uint32_t it = 0; it < d.height * d.tiff.across; it += kTiffExpandPieces) b.lists[L_TIFF_EXPAND].push_back({I, it});
   } else if (d.fmt == kFmtBmp) {
     if (d.bmp.rle) b.lists[L_BMP_RLE].push_back({I, 0});
     for (uint32_t it = 0; it < bmp_row_groups(d.width) * d.height; it += 64) b.lists[L_BMP_EXPAND].push_back({I, it});
@@ -1818,6 +1870,7 @@ dg_status Context::stage_and_upload(const SubmitArgs &a, Slot &sl, Batch &b, con
   if (st) return st;
   for (ImageDesc &d : b.descs) {
     if (d.fmt == kFmtPng && d.png.pal) d.png.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.png.pal - 1);
+    if (d.fmt == kFmtTiff) d.tiff.segs = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.tiff.segs - 1);
     if (d.fmt == kFmtBmp && d.bmp.pal) d.bmp.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.bmp.pal - 1);
     if (d.fmt == kFmtGif) d.gif.pal = (uint64_t)(uintptr_t)((char *)sl.meta.p + b.blob_off + d.gif.pal - 1);
     if (d.enc.active) {

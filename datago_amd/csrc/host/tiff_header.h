@@ -1,0 +1,45 @@
+// tiff_header.h — host-side TIFF walker: the header, the first IFD and the
+// segment (strip or tile) table, no pixel work.
+//
+// Replaces the header half of `image::load_from_memory` for TIFF (image 0.25's
+// TiffDecoder over the tiff crate, restated from its published source and
+// pinned to libtiff as Pillow drives it where the two give the same bytes:
+// DESIGN.md §3 "TIFF").  The segments are decoded and placed on the GPU
+// (dg_tiff.hip).  Plain C++: it also links into tests/native/tiff_emu.cpp.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+namespace dg {
+
+enum TiffStatus { TH_OK = 0, TH_UNSUPPORTED = 1, TH_CORRUPT = 2 };
+enum TiffCompression { TIFF_NONE = 1, TIFF_LZW = 5, TIFF_PACKBITS = 32773 };
+
+// One strip or tile (the layout of TiffSeg, dg_types.h).
+struct TiffSegment {
+  uint32_t off, nbytes;  // the coded bytes in the file
+  uint32_t dec;          // bytes they decode to
+  uint32_t dst;          // where those lie in the image's decoded arena (a multiple of 16)
+};
+
+struct TiffHeader {
+  int status = TH_CORRUPT;
+  const char *why = "";
+  uint32_t width = 0, height = 0;
+  int out_c = 0;           // 1 (L8), 2 (La8), 3 (Rgb8), 4 (Rgba8) = SamplesPerPixel
+  int compression = 0;     // TIFF_*
+  int predictor = 1;       // 1 or 2
+  int invert = 0;          // WhiteIsZero
+  int tiled = 0;
+  uint32_t seg_w = 0, seg_h = 0;    // the tile, or width x RowsPerStrip (at most the height)
+  uint32_t across = 0, down = 0;    // segments per row of segments (1 for strips) and rows of them
+  uint64_t dec_total = 0;           // bytes of the decoded arena
+  std::vector<TiffSegment> segs;    // across x down, row-major
+};
+
+bool is_tiff(const uint8_t *d, size_t n);
+void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h);
+
+}  // namespace dg

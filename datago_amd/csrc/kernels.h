@@ -123,6 +123,11 @@ void launch_gif_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint
 // groups of four pixels of a row (256 outputs) per 64-thread workgroup
 void launch_bmp_rle(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_bmp_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+// TIFF (dg_tiff.hip, option "tiff"): lzw and packbits = one 64-thread workgroup (one wave) per (image, segment),
+// expand = kTiffExpandPieces rows of one segment column per 64-thread workgroup
+void launch_tiff_lzw(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_tiff_packbits(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_tiff_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // lossless WebP (dg_vp8l.hip, option "webp"): decode and inverse = one 64-thread workgroup (one wave) per
 // image, store = 256 pixels per workgroup
 void launch_vp8l_decode(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);

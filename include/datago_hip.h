@@ -63,7 +63,7 @@ typedef enum dg_status {
 } dg_status;
 
 /* Image formats reported by dg_probe. */
-enum { DG_FMT_UNKNOWN = 0, DG_FMT_JPEG = 1, DG_FMT_PNG = 2, DG_FMT_GIF = 3, DG_FMT_WEBP = 4, DG_FMT_BMP = 5 };
+enum { DG_FMT_UNKNOWN = 0, DG_FMT_JPEG = 1, DG_FMT_PNG = 2, DG_FMT_GIF = 3, DG_FMT_WEBP = 4, DG_FMT_BMP = 5, DG_FMT_TIFF = 6 };
 
 /* Mirrors ImageTransformConfig (image_processing.rs:43-70) + ImageEncoding (:24-30). */
 typedef struct dg_image_config {
@@ -112,11 +112,12 @@ typedef struct dg_probe_info {
   int32_t format;         /* DG_FMT_* */
   uint32_t width, height;
   int32_t components;     /* 1 (L8) or 3 (RGB8) for JPEG; 4 (Rgba8 on the logical screen) for GIF;
-                             3 (Rgb8) or 4 (Rgba8) for a lossless or extended WebP and for a BMP */
+                             3 (Rgb8) or 4 (Rgba8) for a lossless or extended WebP and for a BMP;
+                             1 (L8), 2 (La8), 3 or 4 for a TIFF */
   int32_t bit_depth;      /* bits per channel (8; 16 for a 16-bit PNG) */
   int32_t h_samp[4], v_samp[4];
   int32_t progressive, arithmetic, precision, restart_interval;
-  int32_t gpu_supported;  /* 1 if dg_submit would decode it on the GPU with the default options (0 for a GIF, a WebP or a BMP) */
+  int32_t gpu_supported;  /* 1 if dg_submit would decode it on the GPU with the default options (0 for a GIF, a WebP, a BMP or a TIFF) */
 } dg_probe_info;
 
 /* Header-only: lets the caller compute the bucket and size the output before
@@ -368,6 +369,25 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 ending inside a header, the masks or the colour table, bfOffBits inside the headers or
  *                 past the file, an uncompressed pixel array cut short, an unknown info-header size.
  *                 Any other value: DG_ERR_INVALID
+ *   "tiff"        1 = decode TIFF files on the GPU (default 0: DG_ERR_CORRUPT from every entry point, like
+ *                 any format the library does not know; dg_probe names a TIFF either way, DG_FMT_TIFF with
+ *                 gpu_supported 0).  The output is what image 0.25's TiffDecoder returns for
+ *                 load_from_memory, top row first, for the files it and libtiff decode to the same bytes:
+ *                 a classic TIFF of either byte order, its first IFD, chunky, 8 bits per sample;
+ *                 BlackIsZero / WhiteIsZero (inverted) as L8, gray with unassociated alpha as La8, RGB as
+ *                 Rgb8, RGB with unassociated alpha (or no ExtraSamples tag) as Rgba8; compression 1,
+ *                 32773 (PackBits) or 5 (LZW, MSB-first codes); predictor 1 or 2; strips of any
+ *                 RowsPerStrip or tiles whose sides are multiples of 16.  From there the image behaves as
+ *                 an 8-bit PNG of the same pixels (original_* = ImageWidth and ImageLength).
+ *                 DG_ERR_UNSUPPORTED, each with a dg_last_error text of its own: BigTIFF, other sample
+ *                 depths and formats, palette / mask / CMYK / YCbCr / CIELab, PlanarConfiguration 2,
+ *                 FillOrder 2, predictor 3, every other compression, old-style LZW, associated or
+ *                 unspecified extra samples, other tile sizes, an image over 512 MiB or over the GPU
+ *                 path's 32-bit working set, and, found while decoding, an LZW table that stays full
+ *                 for over 1000 codes (libtiff refuses such a stream).  DG_ERR_CORRUPT: a broken IFD, a
+ *                 value, offset or count past the file, a segment table that does not fit the image, and
+ *                 a segment that decodes to fewer bytes than its rows hold.  Any other value:
+ *                 DG_ERR_INVALID
  *   "webp"        1 = decode still lossless WebP files on the GPU: a RIFF/WEBP file whose image data is a
  *                 VP8L chunk, alone (simple file) or behind VP8X with ICCP / EXIF / XMP / unknown chunks
  *                 skipped (default 0: DG_ERR_CORRUPT from every entry point, like any format the library

@@ -1,0 +1,146 @@
+#!/usr/bin/env python
+"""The rate of TIFF files (context option "tiff") beside the paths the same pixels
+could take: a pool of 1024x1536 RGB images (a few distinct seeded photo-like
+images, repeated) written by Pillow (libtiff: 74 strips of 21 rows) as
+
+    raw        uncompressed (4.7 MB each)
+    lzw        LZW
+    lzw_pred   LZW with predictor 2
+    png        the same pixels as an RGB PNG: the nearest existing GPU path
+
+and sent through dg_submit_device, device-resident input and output, by one
+context (crop_and_resize to the 512 / 16 buckets).  Per pool: ms per batch with
+one batch in flight (median), the pipelined rate with three in flight and the
+stages of dg_last_batch_timings.  Beside them, where these files go today:
+Pillow decoding and a Lanczos resize to the bucket's size of the same TIFF
+files on 16 processes (measured before the GPU is opened; the workers never
+touch it).
+
+    python tools/tiff_rate.py [--n 256] [--distinct 2] [--steps 12] [--warmup 3] [--procs 16] [--out r.json]"""
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from bmp_rate import pillow_rate  # noqa: E402  (the same 16-process Pillow leg)
+
+W, H = 1024, 1536
+KINDS = ("raw", "lzw", "lzw_pred", "png")
+TIFFS = KINDS[:3]
+
+
+def make_pool(distinct: int):
+    from PIL import Image
+    from datago_amd import synth
+    pool = {k: [] for k in KINDS}
+    for i in range(distinct):
+        im = Image.fromarray(synth.synth_pixels(np.random.default_rng(900 + i), W, H, False))
+        for kind, kw in (("raw", dict(format="TIFF", compression="raw")), ("lzw", dict(format="TIFF", compression="tiff_lzw")),
+                         ("lzw_pred", dict(format="TIFF", compression="tiff_lzw", tiffinfo={317: 2})), ("png", dict(format="PNG"))):
+            buf = io.BytesIO()
+            im.save(buf, **kw)
+            pool[kind].append(buf.getvalue())
+    return pool
+
+
+def run(ctx, L, files, steps: int, warmup: int, depth: int = 3):
+    offs = np.cumsum([0] + [(len(f) + 15) // 16 * 16 for f in files])[:-1]
+    host = ctx.host_alloc(int(offs[-1]) + len(files[-1]) + 64)
+    for f, o in zip(files, offs):
+        host[int(o):int(o) + len(f)] = np.frombuffer(f, np.uint8)
+    d_in = ctx.alloc(host.nbytes + 64)
+    ctx.h2d(d_in, host)
+    sizes = []
+    for f in files:
+        st, nb = ctx.output_size(f)
+        assert st == L.DG_OK, L.last_error()
+        sizes.append(nb)
+    d_outs = [ctx.alloc(nb) for nb in sizes]
+    ctx.synchronize()
+    hp = [host.ctypes.data + int(o) for o in offs]
+    dp = [d_in + int(o) for o in offs]
+    lens = [len(f) for f in files]
+
+    def once():
+        t0 = time.perf_counter()
+        ticket, metas = ctx.submit_device(hp, dp, lens, d_outs, sizes)
+        ctx.wait(ticket)
+        dt = 1e3 * (time.perf_counter() - t0)
+        assert all(metas[i].status == L.DG_OK for i in range(len(files))), L.last_error()
+        return dt
+
+    ms = [once() for _ in range(warmup + steps)][warmup:]
+    t0, tickets = time.perf_counter(), []
+    for _ in range(steps):
+        tickets.append(ctx.submit_device(hp, dp, lens, d_outs, sizes))
+        if len(tickets) >= depth:
+            t, metas = tickets.pop(0)  # the library writes the metas until the wait returns: keep them
+            ctx.wait(t)
+    for t, metas in tickets:
+        ctx.wait(t)
+    piped = (time.perf_counter() - t0) / steps
+    ctx.set_option("timing", 1)
+    stages = []
+    for _ in range(5):
+        once()
+        stages.append({k: float(v) for k, v in ctx.timings().items()})
+    ctx.set_option("timing", 0)
+    for p in d_outs + [d_in]:
+        ctx.free(p)
+    ctx.host_free(host)
+    med = {k: round(statistics.median(s[k] for s in stages), 4) for k in stages[0]}
+    return {"coded_mb": round(sum(lens) / 2 ** 20, 2), "ms_per_batch": round(statistics.median(ms), 3),
+            "images_per_s_one_in_flight": round(1e3 * len(files) / statistics.median(ms), 1),
+            "images_per_s_pipelined": round(len(files) / piped, 1),
+            "gpx_s_pipelined": round(len(files) * W * H / piped / 1e9, 3),
+            "stages_ms": {k: v for k, v in med.items() if v >= 0.01}}
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=256)
+    ap.add_argument("--distinct", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=12)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--procs", type=int, default=16)
+    ap.add_argument("--no-pillow", action="store_true")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    pool = make_pool(a.distinct)
+    res = {"images": a.n, "distinct": a.distinct, "size": [W, H], "coded_bytes": {k: len(v[0]) for k, v in pool.items()}}
+    from oracle import buckets as B
+    size = B.ARAwareTransform(512, 16, 0.5, 2.0).target_size(W, H)
+    res["bucket"] = list(size)
+    if not a.no_pillow:  # first: forked workers, before this process opens the GPU
+        res["pillow"] = {k: pillow_rate([pool[k][i % a.distinct] for i in range(a.n)], size, a.procs) for k in TIFFS}
+    from datago_amd import _lib as L
+    kw = dict(crop_and_resize=True, default_image_size=512, downsampling_ratio=16, min_aspect_ratio=0.5,
+              max_aspect_ratio=2.0)
+    for kind in KINDS:
+        ctx = L.Context(0, tiff=True, **kw)
+        res[kind] = run(ctx, L, [pool[kind][i % a.distinct] for i in range(a.n)], a.steps, a.warmup)
+        ctx.close()
+    r = lambda k: res[k]["images_per_s_pipelined"]  # noqa: E731
+    for kind in TIFFS:
+        res["%s_over_png" % kind] = round(r(kind) / r("png"), 3)
+        if not a.no_pillow:
+            res["%s_over_pillow" % kind] = round(r(kind) / res["pillow"][kind]["images_per_s"], 2)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
