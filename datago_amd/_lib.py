@@ -334,7 +334,7 @@ class Context:
                  jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False,
                  resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False,
                  jenc_optimize: bool = False, gif: bool = False, webp: bool = False, webp_lossy: bool = False,
-                 webp_alpha: bool = False, bmp: bool = False, tiff: bool = False):
+                 webp_alpha: bool = False, bmp: bool = False, tiff: bool = False, tiff_deflate: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -367,7 +367,9 @@ class Context:
                 # Windows bitmaps: Rgb8, or Rgba8 with an alpha mask; off: DG_ERR_CORRUPT like any unknown format
                 ("bmp", bmp),
                 # 8-bit chunky TIFFs (raw, PackBits, LZW): L8 / La8 / Rgb8 / Rgba8; off: DG_ERR_CORRUPT like any unknown format
-                ("tiff", tiff)):
+                ("tiff", tiff),
+                # with tiff, Deflate-compressed TIFFs (compression 8 / 32946) too; off: DG_ERR_UNSUPPORTED
+                ("tiff_deflate", tiff_deflate)):
             if on:
                 self.set_option(key, 1)
 

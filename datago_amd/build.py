@@ -31,6 +31,7 @@ SOURCES = [
     ("dg_gif.hip", True),
     ("dg_bmp.hip", True),
     ("dg_tiff.hip", True),
+    ("dg_tiff_inflate.hip", True),
     ("dg_vp8l.hip", True),
     ("dg_vp8.hip", True),
     ("dg_alph.hip", True),

@@ -266,20 +266,22 @@ struct TiffSeg {
 struct TiffDesc {
   uint64_t file;      // the file's first byte
   uint64_t segs;      // TiffSeg[nseg] (device)
-  uint64_t dec;       // the decoded arena (compression 5 / 32773)
+  uint64_t dec;       // the decoded arena (compression 5 / 8 / 32773)
   uint32_t nseg;
-  uint32_t comp;      // 1, 5 (LZW) or 32773 (PackBits)
+  uint32_t comp;      // 1, 5 (LZW), 32773 (PackBits) or 8 (Deflate, option "tiff_deflate": k_tiff_inflate, dg_tiff_inflate.hip)
   uint32_t pred;      // 1 or 2
   uint32_t invert;    // WhiteIsZero
   uint32_t spp;       // samples per pixel, 1 .. 4
   uint32_t seg_w;     // pixels per segment row: the tile width, or the image width for strips
   uint32_t seg_h;     // rows per segment: the tile length or RowsPerStrip
   uint32_t across;    // segments side by side: tiles per row, 1 for strips
-  uint32_t fail;      // kTiffFail*: written by k_tiff_lzw / k_tiff_packbits
+  uint32_t fail;      // kTiffFail*: written by k_tiff_lzw / k_tiff_packbits / k_tiff_inflate
 };
 constexpr uint32_t kTiffFailCode = 1;   // an LZW code above the next free one
 constexpr uint32_t kTiffFailShort = 2;  // a segment ends (or its end code comes) before its last byte
 constexpr uint32_t kTiffFailFull = 3;   // an LZW table that stays full for over kTiffFullCodes codes (libtiff refuses it)
+constexpr uint32_t kTiffFailStream = 4; // a zlib header, block header, code set, code or distance that zlib refuses
+constexpr uint32_t kTiffFailSum = 5;    // the Adler-32 after the last block differs from the decoded bytes'
 
 // ---- lossless WebP (ImageDesc::fmt == kFmtWebp, option "webp"): a VP8L chunk as Rgb8 / Rgba8.
 // k_vp8l_decode (one wave per image, dg_vp8l.h) reads the bitstream after the 5-byte header in place:

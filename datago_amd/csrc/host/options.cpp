@@ -241,7 +241,7 @@ const int kNumOptions = (int)(sizeof(kOptionTable) / sizeof(kOptionTable[0]));
 // exactly that list, so a later option stands here, with a test of its own
 // (tests/test_vp8_cpu.py for "webp_lossy", tests/test_alph_cpu.py for
 // "webp_alpha", tests/test_bmp_cpu.py for "bmp", tests/test_tiff_cpu.py for
-// "tiff").  find_option looks through both,
+// "tiff", tests/test_tiff_deflate_cpu.py for "tiff_deflate").  find_option looks through both,
 // so to dg_ctx_set_option the two tables are one.
 const OptRow kOptionTableAdded[] = {
     // Still lossy WebP files (a `VP8 ` image chunk, simple or behind VP8X, no
@@ -297,6 +297,18 @@ const OptRow kOptionTableAdded[] = {
     // segment DG_ERR_CORRUPT.  dg_probe names a TIFF either way and keeps
     // describing the default options.
     STRICT("tiff", tiff),
+    // With "tiff" (alone it changes nothing): a TIFF of compression 8 (Adobe
+    // Deflate) or 32946 (the older code for the same zlib stream), predictor 1
+    // or 2, decodes like an LZW one (default off: it stays DG_ERR_UNSUPPORTED
+    // "TIFF: compression other than none, LZW and PackBits").  k_tiff_inflate
+    // (dg_tiff_inflate.hip) inflates one segment per wave into the decoded
+    // arena; k_tiff_expand goes on from there.  A segment is refused as
+    // DG_ERR_CORRUPT with a text where zlib under libtiff refuses it: a bad
+    // zlib header or preset dictionary, block type 3, LEN / NLEN, an
+    // over-subscribed or incomplete code set, a missing end-of-block code, an
+    // invalid code, a distance before the segment's first byte, data that ends
+    // early, and a wrong Adler-32 where the stream ends at the last byte.
+    STRICT("tiff_deflate", tiff_deflate),
 };
 const int kNumOptionsAdded = (int)(sizeof(kOptionTableAdded) / sizeof(kOptionTableAdded[0]));
 

@@ -1112,7 +1112,7 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     C = (uint32_t)p.bmp.out_c;
   } else if (opt_.tiff && is_tiff(h, len)) {  // option "tiff"
     p.fmt = kFmtTiff;
-    parse_tiff_header(h, len, p.tiff);
+    parse_tiff_header(h, len, p.tiff, opt_.tiff_deflate);  // option "tiff_deflate" admits compression 8 / 32946
     if (p.tiff.status != TH_OK) {
       p.status = p.tiff.status == TH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
       return DG_OK;
@@ -1516,6 +1516,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   if (!from_fix && b.any_tiff) {  // TIFF: every coded segment -> its bytes in the decoded arena
     launch_tiff_lzw(sl.st, dm, lst(L_TIFF_LZW), cnt(L_TIFF_LZW));
     launch_tiff_packbits(sl.st, dm, lst(L_TIFF_PACKBITS), cnt(L_TIFF_PACKBITS));
+    launch_tiff_inflate(sl.st, dm, lst(L_TIFF_INFLATE), cnt(L_TIFF_INFLATE));  // (option "tiff_deflate")
   }
   if (!from_fix && b.any_webp) {  // lossless WebP: bitstream -> ARGB plane -> inverse transforms
     launch_vp8l_decode(sl.st, dm, lst(L_VP8L), cnt(L_VP8L));
@@ -1908,11 +1909,13 @@ dg_status Context::finish_body(Slot &sl) {
                 : f == kBmpFailPalette ? "BMP: pixel index past the colour table"
                                        : "BMP: decode failed");
     }
-    if (status && back[b.desc_of[i]].fmt == kFmtTiff) {  // what k_tiff_lzw / k_tiff_packbits met in a segment
+    if (status && back[b.desc_of[i]].fmt == kFmtTiff) {  // what k_tiff_lzw / k_tiff_packbits / k_tiff_inflate met in a segment
       const uint32_t f = back[b.desc_of[i]].tiff.fail;
       set_error(f == kTiffFailCode    ? "TIFF: LZW code above the next free code"
                 : f == kTiffFailShort ? "TIFF: a segment's data ends before its last row is complete"
                 : f == kTiffFailFull  ? "TIFF: LZW table stays full without a clear code"
+                : f == kTiffFailStream ? "TIFF: malformed Deflate stream (zlib header, block header, code set, code or distance)"
+                : f == kTiffFailSum   ? "TIFF: Adler-32 of a Deflate segment does not match its bytes"
                                       : "TIFF: decode failed");
     }
     if (status && back[b.desc_of[i]].fmt == kFmtWebp) {  // what k_vp8l_decode met in the stream

@@ -81,8 +81,8 @@ struct Batch {
   std::vector<ImageDesc> descs;
   std::vector<int> desc_of;           // image -> desc index or -1
   // workgroup lists (host copies) and their offsets in the device meta buffer
-  std::vector<WgItem> lists[58];
-  size_t list_off[58] = {0};
+  std::vector<WgItem> lists[64];
+  size_t list_off[64] = {0};
   // PNG: IDAT gather jobs and palettes, uploaded with the descriptors
   std::vector<GatherJob> gjobs;
   size_t gjob_off = 0;
@@ -104,7 +104,7 @@ struct Batch {
   bool any_webp = false;  // a lossless WebP (option "webp") or a VP8L-coded alpha stream: k_vp8l_decode, k_vp8l_inverse, k_vp8l_store
   bool any_alph = false;  // a lossy WebP with an ALPH chunk (option "webp_alpha"): k_alph_plane
   bool any_bmp = false;   // a BMP (option "bmp"): k_bmp_rle, k_bmp_expand
-  bool any_tiff = false;  // a TIFF (option "tiff"): k_tiff_lzw, k_tiff_packbits, k_tiff_expand
+  bool any_tiff = false;  // a TIFF (option "tiff"): k_tiff_lzw, k_tiff_packbits, k_tiff_inflate, k_tiff_expand
   bool any_vp8 = false;   // a lossy WebP (option "webp_lossy"): k_vp8_parse, k_vp8_recon, k_vp8_filter, k_vp8_rgb
   bool penc_dyn = false;  // a PNG re-encode with option "penc_dynamic": histogram, k_penc_tree, dynamic count / write
   bool jenc_opt = false;  // a JPEG re-encode with option "jenc_optimize": k_enc_hist, k_enc_tree, per-image tables
@@ -225,9 +225,10 @@ enum ListId {
   L_ALPH,                                                   // its alpha plane (dg_alph.hip): per item of alph_items
   L_BMP_RLE, L_BMP_EXPAND,                                  // BMP decode (dg_bmp.hip): per RLE image, per 64 groups of 4 pixels
   L_TIFF_LZW, L_TIFF_PACKBITS, L_TIFF_EXPAND,               // TIFF decode (dg_tiff.hip): per LZW / PackBits segment, per 4 row pieces
+  L_TIFF_INFLATE,                                           // TIFF Deflate (dg_tiff_inflate.hip): per Deflate segment
   L_COUNT
 };
-static_assert((int)L_COUNT <= 58, "Batch::lists");
+static_assert((int)L_COUNT <= 64, "Batch::lists");
 
 // A recently pooled table (pool_huff / pool_quant): its key bytes and slot.
 struct RecentTab {

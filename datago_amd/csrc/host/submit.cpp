@@ -1740,7 +1740,7 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
     b.lists[L_VP8L].push_back({I, 0});
     for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_VP8L_STORE].push_back({I, it});
   } else if (d.fmt == kFmtTiff) {
-    const ListId dec = d.tiff.comp == TIFF_LZW ? L_TIFF_LZW : L_TIFF_PACKBITS;
+    const ListId dec = d.tiff.comp == TIFF_LZW ? L_TIFF_LZW : d.tiff.comp == TIFF_DEFLATE ? L_TIFF_INFLATE : L_TIFF_PACKBITS;
     for (uint32_t sg = 0; d.tiff.comp != TIFF_NONE && sg < d.tiff.nseg; sg++) b.lists[dec].push_back({I, sg});
     for (uint32_t it = 0; it < d.height * d.tiff.across; it += kTiffExpandPieces) b.lists[L_TIFF_EXPAND].push_back({I, it});
   } else if (d.fmt == kFmtBmp) {

@@ -41,7 +41,7 @@ struct Entry {
 };
 }  // namespace
 
-void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h) {
+void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate) {
   h = TiffHeader();
   if (!is_tiff(d, n)) return fail(h, TH_CORRUPT, "not a TIFF");
   const Reader r{d, n, d[0] == 'M'};
@@ -77,7 +77,8 @@ void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h) {
   h.height = one(T_H, 0);
   if (h.width == 0 || h.height == 0) return fail(h, TH_UNSUPPORTED, "TIFF: zero dimension");
   // ---- what the GPU path does not take
-  const uint32_t spp = one(T_SPP, 1), photo = one(T_PHOTO, 0), comp = one(T_COMP, 1), pred = one(T_PRED, 1);
+  const uint32_t spp = one(T_SPP, 1), photo = one(T_PHOTO, 0), pred = one(T_PRED, 1);
+  const uint32_t comp = deflate && one(T_COMP, 1) == 32946u ? (uint32_t)TIFF_DEFLATE : one(T_COMP, 1);  // one zlib stream under either code
   if (spp == 0 || spp > 4) return fail(h, TH_UNSUPPORTED, "TIFF: more than four samples per pixel");
   if (e[T_BITS].present && e[T_BITS].count != spp && !(e[T_BITS].count == 1 && spp == 1))
     return fail(h, TH_UNSUPPORTED, "TIFF: BitsPerSample count differs from SamplesPerPixel");
@@ -91,10 +92,10 @@ void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h) {
   if (one(T_FILL, 1) != 1) return fail(h, TH_UNSUPPORTED, "TIFF: FillOrder 2");
   if (pred == 3) return fail(h, TH_UNSUPPORTED, "TIFF: floating-point predictor");
   if (pred != 1 && pred != 2) return fail(h, TH_UNSUPPORTED, "TIFF: unknown predictor");
-  if (comp != TIFF_NONE && comp != TIFF_LZW && comp != TIFF_PACKBITS)
+  if (comp != TIFF_NONE && comp != TIFF_LZW && comp != TIFF_PACKBITS && !(deflate && comp == TIFF_DEFLATE))
     return fail(h, TH_UNSUPPORTED, "TIFF: compression other than none, LZW and PackBits");
-  if (pred == 2 && comp != TIFF_LZW)  // libtiff has no predictor in these codecs and ignores the tag; the tiff crate applies it
-    return fail(h, TH_UNSUPPORTED, "TIFF: predictor without LZW");
+  // libtiff has no predictor in the raw and PackBits codecs and ignores the tag; the tiff crate applies it.  Its ZIP codec has one.
+  if (pred == 2 && comp != TIFF_LZW && comp != TIFF_DEFLATE) return fail(h, TH_UNSUPPORTED, "TIFF: predictor without LZW");
   // samples and the extra one: libtiff (Pillow) and the tiff crate agree on these forms only
   const bool gray = photo < 2;
   const uint32_t colour = gray ? 1u : 3u;

@@ -15,7 +15,7 @@
 namespace dg {
 
 enum TiffStatus { TH_OK = 0, TH_UNSUPPORTED = 1, TH_CORRUPT = 2 };
-enum TiffCompression { TIFF_NONE = 1, TIFF_LZW = 5, TIFF_PACKBITS = 32773 };
+enum TiffCompression { TIFF_NONE = 1, TIFF_LZW = 5, TIFF_DEFLATE = 8, TIFF_PACKBITS = 32773 };  // (32946, the older Deflate code, is stored as 8)
 
 // One strip or tile (the layout of TiffSeg, dg_types.h).
 struct TiffSegment {
@@ -40,6 +40,7 @@ struct TiffHeader {
 };
 
 bool is_tiff(const uint8_t *d, size_t n);
-void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h);
+// deflate (option "tiff_deflate"): compression 8 and 32946 pass, with predictor 1 or 2; without it they are TH_UNSUPPORTED.
+void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate = false);
 
 }  // namespace dg

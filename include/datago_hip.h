@@ -388,7 +388,20 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 value, offset or count past the file, a segment table that does not fit the image, and
  *                 a segment that decodes to fewer bytes than its rows hold.  Any other value:
  *                 DG_ERR_INVALID
- *   "webp"        1 = decode still lossless WebP files on the GPU: a RIFF/WEBP file whose image data is a
+ *   "tiff_deflate" 1 = with "tiff" (alone it changes nothing), a TIFF of compression 8 (Adobe Deflate) or
+ *                 32946 (the older code for the same zlib stream) decodes as well, with predictor 1 or 2
+ *                 (default 0: such a file stays DG_ERR_UNSUPPORTED "TIFF: compression other than none, LZW
+ *                 and PackBits").  A segment is one zlib stream; decoding ends when the segment's bytes
+ *                 exist, as in libtiff.  DG_ERR_CORRUPT with a dg_last_error text, found while decoding: a
+ *                 zlib header that is not deflate with a window of at most 32 KiB, fails its check bits or
+ *                 asks for a preset dictionary; block type 3; a stored block whose LEN and NLEN disagree;
+ *                 an over-subscribed or incomplete code set, a missing end-of-block code, a repeat with
+ *                 nothing before it or past the counts, an invalid literal/length or distance code; a
+ *                 distance before the segment's first byte; data that ends early; and an Adler-32 that
+ *                 differs, where the final block ends at the segment's last byte and the four bytes are
+ *                 there.  Distances are not held to the header's window size (zlib does not either).  Any
+ *                 other value: DG_ERR_INVALID
+ *   "webp"     1 = decode still lossless WebP files on the GPU: a RIFF/WEBP file whose image data is a
  *                 VP8L chunk, alone (simple file) or behind VP8X with ICCP / EXIF / XMP / unknown chunks
  *                 skipped (default 0: DG_ERR_CORRUPT from every entry point, like any format the library
  *                 does not know; dg_probe names such a file either way, DG_FMT_WEBP with gpu_supported 0).

@@ -6,6 +6,8 @@ images, repeated) written by Pillow (libtiff: 74 strips of 21 rows) as
     raw        uncompressed (4.7 MB each)
     lzw        LZW
     lzw_pred   LZW with predictor 2
+    deflate       Adobe Deflate (option "tiff_deflate")
+    deflate_pred  Adobe Deflate with predictor 2
     png        the same pixels as an RGB PNG: the nearest existing GPU path
 
 and sent through dg_submit_device, device-resident input and output, by one
@@ -34,8 +36,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from bmp_rate import pillow_rate  # noqa: E402  (the same 16-process Pillow leg)
 
 W, H = 1024, 1536
-KINDS = ("raw", "lzw", "lzw_pred", "png")
-TIFFS = KINDS[:3]
+KINDS = ("raw", "lzw", "lzw_pred", "deflate", "deflate_pred", "png")
+TIFFS = KINDS[:5]
 
 
 def make_pool(distinct: int):
@@ -45,7 +47,10 @@ def make_pool(distinct: int):
     for i in range(distinct):
         im = Image.fromarray(synth.synth_pixels(np.random.default_rng(900 + i), W, H, False))
         for kind, kw in (("raw", dict(format="TIFF", compression="raw")), ("lzw", dict(format="TIFF", compression="tiff_lzw")),
-                         ("lzw_pred", dict(format="TIFF", compression="tiff_lzw", tiffinfo={317: 2})), ("png", dict(format="PNG"))):
+                         ("lzw_pred", dict(format="TIFF", compression="tiff_lzw", tiffinfo={317: 2})),
+                         ("deflate", dict(format="TIFF", compression="tiff_adobe_deflate")),
+                         ("deflate_pred", dict(format="TIFF", compression="tiff_adobe_deflate", tiffinfo={317: 2})),
+                         ("png", dict(format="PNG"))):
             buf = io.BytesIO()
             im.save(buf, **kw)
             pool[kind].append(buf.getvalue())
@@ -126,7 +131,7 @@ def main() -> int:
     kw = dict(crop_and_resize=True, default_image_size=512, downsampling_ratio=16, min_aspect_ratio=0.5,
               max_aspect_ratio=2.0)
     for kind in KINDS:
-        ctx = L.Context(0, tiff=True, **kw)
+        ctx = L.Context(0, tiff=True, tiff_deflate=True, **kw)
         res[kind] = run(ctx, L, [pool[kind][i % a.distinct] for i in range(a.n)], a.steps, a.warmup)
         ctx.close()
     r = lambda k: res[k]["images_per_s_pipelined"]  # noqa: E731
