@@ -279,7 +279,7 @@ def meta_status(metas) -> np.ndarray:
 def payload_array(buf: np.ndarray, m: PayloadMeta) -> np.ndarray:
     """The HWC pixels of a decoded payload over the bytes of `buf` (a uint8
     output buffer), without a copy: uint16 samples in native byte order when
-    meta.bit_depth == 16 (context option "png16"), uint8 otherwise.  An
+    meta.bit_depth == 16 (context options "png16", "tiff16"), uint8 otherwise.  An
     encoded payload (pre_encode_images) is its file's bytes, flat."""
     a = buf[: m.nbytes]
     if m.is_encoded:
@@ -334,7 +334,8 @@ class Context:
                  jpeg_quality: int = 92, decode_semantics: int = 0, png16: bool = False,
                  resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False,
                  jenc_optimize: bool = False, gif: bool = False, webp: bool = False, webp_lossy: bool = False,
-                 webp_alpha: bool = False, bmp: bool = False, tiff: bool = False, tiff_deflate: bool = False):
+                 webp_alpha: bool = False, bmp: bool = False, tiff: bool = False, tiff_deflate: bool = False,
+                 tiff16: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -369,7 +370,9 @@ class Context:
                 # 8-bit chunky TIFFs (raw, PackBits, LZW): L8 / La8 / Rgb8 / Rgba8; off: DG_ERR_CORRUPT like any unknown format
                 ("tiff", tiff),
                 # with tiff, Deflate-compressed TIFFs (compression 8 / 32946) too; off: DG_ERR_UNSUPPORTED
-                ("tiff_deflate", tiff_deflate)):
+                ("tiff_deflate", tiff_deflate),
+                # with tiff, TIFFs of 16-bit samples too: L16 / La16 / Rgb16 / Rgba16 as uint16; off: DG_ERR_UNSUPPORTED
+                ("tiff16", tiff16)):
             if on:
                 self.set_option(key, 1)
 

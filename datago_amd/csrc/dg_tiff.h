@@ -15,7 +15,8 @@
 //
 // Expand.  A lane holds four pixels as four dwords, sample s of a pixel in byte s
 // (tiff_px); predictor 2 is a prefix sum per byte lane, modulo 256 (tiff_badd), and
-// tiff_pack turns the four pixels back into the 4 x spp bytes of the row.
+// tiff_pack turns the four pixels back into the 4 x spp bytes of the row.  The 16-bit form
+// (k_tiff_expand16; tests/native/tiff16_emu.cpp on the CPU) is the tiff16_* routines below.
 #pragma once
 #include "dg_gif.h"
 #include "dg_types.h"
@@ -65,9 +66,44 @@ DG_HD uint32_t tiff_pack(const uint32_t p[4], uint32_t k, uint32_t spp) {
   if (spp == 2u) return p[2u * k] | (p[2u * k + 1u] << 16);
   return k == 0u ? p[0] | (p[1] << 24) : k == 1u ? (p[1] >> 8) | (p[2] << 16) : (p[2] >> 16) | (p[3] << 8);
 }
+// ---- expand, 16-bit samples (k_tiff_expand16, option "tiff16")
+// A lane's four pixels are 4 x spp samples in 2 x spp dwords, two samples to a dword in row order (sample j
+// in half j & 1 of dword j >> 1).  For predictor 2 a pixel's samples are regrouped into ceil(spp / 2) dwords of
+// its own (tiff16_px: sample c in half c & 1 of dword c >> 1, the spare half of an odd spp zero), so the sum
+// with stride spp is one packed add per pixel dword, modulo 65536 per half (tiff16_hadd); tiff16_pack goes back.
+// Both halves of v with their two bytes exchanged: an MM file's samples, two at a time.
+DG_HD uint32_t tiff16_swap(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_perm(v, v, 0x02030001u);
+#else
+  return ((v & 0x00FF00FFu) << 8) | ((v >> 8) & 0x00FF00FFu);
+#endif
+}
+// Half-wise a + b modulo 65536 on two packed samples.
+DG_HD uint32_t tiff16_hadd(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b));  // v_pk_add_u16
+#else
+  return ((a & 0x7FFF7FFFu) + (b & 0x7FFF7FFFu)) ^ ((a ^ b) & 0x80008000u);
+#endif
+}
+// Sample j of samples packed two to a dword.
+DG_HD uint32_t tiff16_at(const uint32_t *v, uint32_t j) { return (v[j >> 1] >> (16u * (j & 1u))) & 0xFFFFu; }
+// Dword k (< ceil(spp / 2)) of pixel t (< 4) of the row dwords v.
+DG_HD uint32_t tiff16_px(const uint32_t *v, uint32_t t, uint32_t k, uint32_t spp) {
+  const uint32_t j = t * spp + 2u * k;
+  return tiff16_at(v, j) | (2u * k + 1u < spp ? tiff16_at(v, j + 1u) << 16 : 0u);
+}
+// Dword m (< 2 spp) of the row from the four pixels' dwords p[t][k].
+DG_HD uint32_t tiff16_pack(const uint32_t p[4][2], uint32_t m, uint32_t spp) {
+  const uint32_t j0 = 2u * m, j1 = j0 + 1u;
+  return tiff16_at(p[j0 / spp], j0 % spp) | (tiff16_at(p[j1 / spp], j1 % spp) << 16);
+}
+
 // Row piece pc of an image (a piece is one row of one segment column, pieces run row by row): its image
 // row, its segment, the byte offset of its first pixel inside the segment, its first pixel in the row and
-// its pixel count (an edge tile's padding columns are dropped).
+// its pixel count (an edge tile's padding columns are dropped).  spp: bytes per pixel (16-bit samples: 2 x spp).
 struct TiffPiece {
   uint32_t y, seg, off, px0, npx;
 };

@@ -4,6 +4,8 @@
 //   k_tiff_packbits  one segment's PackBits stream -> its bytes in the decoded arena
 //   k_tiff_expand    decoded (compression 1: the file's own) segment bytes -> the pixel plane:
 //                    predictor 2, WhiteIsZero, strip and tile placement, the edge crop
+//   k_tiff_expand16  the same for 16-bit samples (option "tiff16"): the file's byte order undone,
+//                    predictor 2 on whole samples, native-endian uint16 in the pixel plane
 //
 // What they restate: the tiff crate as image 0.25's TiffDecoder drives it for
 // load_from_memory, for the files it and libtiff (Pillow) decode to the same bytes;
@@ -39,6 +41,12 @@
 // modulo 256: a lane sums its own four pixels per sample, the 64 lane totals are
 // scanned with cross-lane shuffles and added back; the carry runs on to the next 256
 // pixels of the row.
+//
+// k_tiff_expand16 keeps that split of the work.  A lane's four pixels are 2 x spp dwords with two
+// samples each, funnel-shifted from aligned loads at one of four byte phases; an MM file's
+// samples are swapped two at a time by one byte permute; predictor 2 regroups a pixel's samples
+// into ceil(spp / 2) dwords so that the sums are packed 16-bit adds (v_pk_add_u16), scanned over
+// the wave as above; the stores are 16 bytes wide for spp 2 and 4, 8 bytes for spp 1 and 3.
 //
 // Every loop is bounded by the segment's bit or byte count and its decoded size: a
 // step consumes input or ends the decode.
@@ -426,6 +434,106 @@ __global__ __launch_bounds__(64) void k_tiff_expand(ImageDesc *__restrict__ imgs
   }
 }
 
+// ------------------------------------------------------------ expand, 16-bit samples
+
+// One row of one segment column (npx pixels of SPP 16-bit samples from `row`, at any byte phase) to `dst` as
+// native-endian uint16: 256 pixels per trip, a lane four of them = 2 x SPP dwords, two samples to a dword.
+template <uint32_t SPP>
+__device__ __forceinline__ void tiff_row16(uint64_t row, uint64_t end, DG_GLOBAL uint8_t *dst, uint32_t npx, bool pred, bool swap,
+                                           uint32_t lane) {
+  constexpr uint32_t ND = 2u * SPP, PD = (SPP + 1u) / 2u;  // dwords of a lane's row bytes, dwords of one pixel
+  uint32_t carry[PD];  // predictor 2: the sample sums up to this trip's first pixel
+#pragma unroll
+  for (uint32_t k = 0; k < PD; k++) carry[k] = 0u;
+  for (uint32_t q0 = 0; q0 < npx; q0 += 256u) {
+    const uint32_t x0 = q0 + 4u * lane;
+    const uint32_t n = x0 >= npx ? 0u : npx - x0 < 4u ? npx - x0 : 4u;
+    const uint64_t A = row + (uint64_t)x0 * ND, last = A + n * ND, A0 = A & ~3ull;
+    const uint32_t sh = (uint32_t)(A & 3ull) * 8u;  // four phases: an odd one puts every sample across a dword boundary
+    uint32_t r[ND + 1], v[ND];
+#pragma unroll
+    for (uint32_t k = 0; k <= ND; k++) r[k] = A0 + 4u * k < last ? tiff_ld32(A0 + 4u * k, end) : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < ND; k++) v[k] = __funnelshift_r(r[k], r[k + 1], sh);
+    if (swap) {
+#pragma unroll
+      for (uint32_t k = 0; k < ND; k++) v[k] = tiff16_swap(v[k]);
+    }
+    if (pred) {
+      uint32_t p[4][2], x[PD];
+#pragma unroll
+      for (uint32_t t = 0; t < 4; t++) {
+#pragma unroll
+        for (uint32_t k = 0; k < 2; k++) p[t][k] = k < PD ? tiff16_px(v, t, k, SPP) : 0u;
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < PD; k++) {
+#pragma unroll
+        for (uint32_t t = 1; t < 4; t++) p[t][k] = tiff16_hadd(p[t][k], p[t - 1][k]);
+        x[k] = p[3][k];  // the lane's total; inclusive scan over the lanes
+      }
+#pragma unroll
+      for (uint32_t d = 1; d < 64; d <<= 1) {
+#pragma unroll
+        for (uint32_t k = 0; k < PD; k++) {
+          const uint32_t y = __shfl_up(x[k], d);
+          if (lane >= d) x[k] = tiff16_hadd(x[k], y);
+        }
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < PD; k++) {
+        const uint32_t before = __shfl_up(x[k], 1);
+        const uint32_t add = lane ? tiff16_hadd(carry[k], before) : carry[k];
+#pragma unroll
+        for (uint32_t t = 0; t < 4; t++) p[t][k] = tiff16_hadd(p[t][k], add);
+        carry[k] = tiff16_hadd(carry[k], __shfl(x[k], 63));
+      }
+#pragma unroll
+      for (uint32_t m = 0; m < ND; m++) v[m] = tiff16_pack(p, m, SPP);
+    }
+    DG_GLOBAL uint8_t *o = dst + (size_t)x0 * ND;
+    if (n == 4u) {  // 8 x SPP bytes on an 8 x SPP / gcd(SPP, 2)-byte boundary: x0 and the segment column's first pixel are multiples of 4
+      if (SPP % 2u == 0u) {
+#pragma unroll
+        for (uint32_t k = 0; k < ND; k += 4) *(DG_GLOBAL u32x4 *)(o + 4u * k) = u32x4{v[k], v[k + 1], v[k + 2], v[k + 3]};
+      } else {
+#pragma unroll
+        for (uint32_t k = 0; k < ND; k += 2) *(DG_GLOBAL u32x2 *)(o + 4u * k) = u32x2{v[k], v[k + 1]};
+      }
+    } else {  // the row's ragged end, by samples
+#pragma unroll
+      for (uint32_t j = 0; j < 3u * SPP; j++)
+        if (j < n * SPP) ((DG_GLOBAL uint16_t *)o)[j] = (uint16_t)tiff16_at(v, j);
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void k_tiff_expand16(ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  const WgItem it = list[blockIdx.x];
+  ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  const TiffDesc &g = im.tiff;
+  const uint32_t lane = threadIdx.x, W = im.width, bpp = 2u * g.spp;
+  const uint32_t pieces = im.height * g.across;
+  for (uint32_t pc = it.item0; pc < it.item0 + kTiffExpandPieces && pc < pieces; pc++) {
+    const TiffPiece pp = tiff_piece(pc, W, bpp, g.seg_w, g.seg_h, g.across);
+    const TiffSeg sg = tiff_seg(g.segs, pp.seg);
+    const uint64_t base = g.comp == 1u ? g.file + sg.off : g.dec + sg.dst;
+    const uint64_t end = base + (g.comp == 1u ? sg.nbytes : sg.dec);
+    const uint64_t row = base + pp.off;
+    DG_GLOBAL uint8_t *dst = gp<uint8_t>(im.pix) + (size_t)pp.y * im.pix_stride + (size_t)pp.px0 * bpp;
+    const bool pred = g.pred == 2u, swap = g.swap != 0u;
+    if (g.spp == 1u)
+      tiff_row16<1>(row, end, dst, pp.npx, pred, swap, lane);
+    else if (g.spp == 2u)
+      tiff_row16<2>(row, end, dst, pp.npx, pred, swap, lane);
+    else if (g.spp == 3u)
+      tiff_row16<3>(row, end, dst, pp.npx, pred, swap, lane);
+    else
+      tiff_row16<4>(row, end, dst, pp.npx, pred, swap, lane);
+  }
+}
+
 // ------------------------------------------------------------ launchers
 
 void launch_tiff_lzw(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
@@ -436,6 +544,9 @@ void launch_tiff_packbits(hipStream_t st, ImageDesc *imgs, const WgItem *list, u
 }
 void launch_tiff_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   if (nwg) hipLaunchKernelGGL(k_tiff_expand, dim3(nwg), dim3(64), 0, st, imgs, list);
+}
+void launch_tiff_expand16(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_tiff_expand16, dim3(nwg), dim3(64), 0, st, imgs, list);
 }
 
 }  // namespace dg

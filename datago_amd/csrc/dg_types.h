@@ -256,7 +256,9 @@ constexpr uint32_t kBmpFailPalette = 4;  // an index at or past the colour table
 // k_tiff_packbits give one wave to every (image, segment) and write the segment's bytes into the
 // decoded arena; k_tiff_expand reads them, or for compression 1 the file's own bytes, undoes predictor 2,
 // inverts WhiteIsZero and places rows and tiles in the pixel plane (dg_tiff.h, dg_tiff.hip).  A
-// segment that does not decode sets ImageDesc::status and TiffDesc::fail names it.
+// segment that does not decode sets ImageDesc::status and TiffDesc::fail names it.  With option "tiff16"
+// a file of 16-bit samples goes through k_tiff_expand16 instead and leaves L16 / La16 / Rgb16 / Rgba16 as
+// native-endian uint16 (ImageDesc::sample_bytes 2: the plane k_png_expand16 leaves).
 struct TiffSeg {
   uint32_t off;     // the coded bytes: offset in the file (any byte alignment) ...
   uint32_t nbytes;  // ... and count
@@ -276,6 +278,8 @@ struct TiffDesc {
   uint32_t seg_h;     // rows per segment: the tile length or RowsPerStrip
   uint32_t across;    // segments side by side: tiles per row, 1 for strips
   uint32_t fail;      // kTiffFail*: written by k_tiff_lzw / k_tiff_packbits / k_tiff_inflate
+  uint32_t bits;      // bits per sample: 8, or 16 (option "tiff16": k_tiff_expand16 instead of k_tiff_expand)
+  uint32_t swap;      // 16-bit samples of an MM file: their bytes are exchanged on the way to the pixel plane
 };
 constexpr uint32_t kTiffFailCode = 1;   // an LZW code above the next free one
 constexpr uint32_t kTiffFailShort = 2;  // a segment ends (or its end code comes) before its last byte

@@ -241,8 +241,9 @@ const int kNumOptions = (int)(sizeof(kOptionTable) / sizeof(kOptionTable[0]));
 // exactly that list, so a later option stands here, with a test of its own
 // (tests/test_vp8_cpu.py for "webp_lossy", tests/test_alph_cpu.py for
 // "webp_alpha", tests/test_bmp_cpu.py for "bmp", tests/test_tiff_cpu.py for
-// "tiff", tests/test_tiff_deflate_cpu.py for "tiff_deflate").  find_option looks through both,
-// so to dg_ctx_set_option the two tables are one.
+// "tiff", tests/test_tiff_deflate_cpu.py for "tiff_deflate", tests/test_tiff16_cpu.py
+// for "tiff16").  find_option looks through both, so to dg_ctx_set_option the
+// two tables are one.
 const OptRow kOptionTableAdded[] = {
     // Still lossy WebP files (a `VP8 ` image chunk, simple or behind VP8X, no
     // ALPH chunk) on the GPU (default off: nothing changes, see "webp").  1,
@@ -309,6 +310,19 @@ const OptRow kOptionTableAdded[] = {
     // invalid code, a distance before the segment's first byte, data that ends
     // early, and a wrong Adler-32 where the stream ends at the last byte.
     STRICT("tiff_deflate", tiff_deflate),
+    // With "tiff" (alone it changes nothing): a TIFF whose samples all have 16
+    // bits, SampleFormat absent or 1, in either byte order, decodes to L16 /
+    // La16 / Rgb16 / Rgba16 as native-endian uint16 with bit_depth 16, or to
+    // Rgb8 under image_to_rgb8 (default off: it stays DG_ERR_UNSUPPORTED
+    // "TIFF: samples not 8 bits").  Compression, predictor, strips and tiles
+    // follow the 8-bit rules; predictor 2 sums whole samples modulo 65536
+    // after the byte order is undone.  k_tiff_expand16 (dg_tiff.hip) takes the
+    // decoded segment bytes to the pixel plane k_png_expand16 leaves of a
+    // 16-bit PNG, so from there the image needs what that PNG needs: nothing
+    // at its bucket's size, "resize16" otherwise, "penc16" into the PNG
+    // encoder; into the JPEG encoder it is DG_ERR_UNSUPPORTED.  16-bit
+    // WhiteIsZero is refused: libtiff and the tiff crate disagree on it.
+    STRICT("tiff16", tiff16),
 };
 const int kNumOptionsAdded = (int)(sizeof(kOptionTableAdded) / sizeof(kOptionTableAdded[0]));
 

@@ -1013,11 +1013,20 @@ dg_status Context::upload_pools() {
 // "resize16"): resize_to_fill's geometry, the tap counts of both passes and
 // the samples of a decoded row that the f32 intermediate holds -- it covers
 // the crop window's rows and the columns the cropped outputs' taps read.
-// False (p.png.why set) where the GPU path does not take the image.
+// False (the format's why set) where the GPU path does not take the image.
+// Why a 16-bit image stays off the GPU path, in its format's words: a PNG's through p.png.why, a TIFF's through p.tiff.why.
+static void deep_why(ImagePlan &p, const char *png, const char *tiff) {
+  if (p.fmt == kFmtTiff)
+    p.tiff.why = tiff;
+  else
+    p.png.why = png;
+}
+
 static bool plan_r16(uint32_t W, uint32_t H, uint32_t C, uint32_t ow, uint32_t oh, ImagePlan &p) {
   p.r16 = true;
   if (!r16_geom(W, H, ow, oh, p.r16g)) {
-    p.png.why = "PNG: 16-bit resize whose scaled size does not cover the bucket";
+    deep_why(p, "PNG: 16-bit resize whose scaled size does not cover the bucket",
+             "TIFF: 16-bit resize whose scaled size does not cover the bucket");
     return false;
   }
   const R16Geom &g = p.r16g;
@@ -1043,7 +1052,8 @@ static bool plan_r16(uint32_t W, uint32_t H, uint32_t C, uint32_t ow, uint32_t o
   // the intermediate and the tap tables stay 32-bit addressable, like the decoder's working set
   if ((uint64_t)p.r16_ns * 4 * oh >= (1ull << 31) || (uint64_t)oh * p.r16_kv * 4 >= (1ull << 31) ||
       (uint64_t)ow * p.r16_kh * 4 >= (1ull << 31)) {
-    p.png.why = "PNG: 16-bit resize whose f32 intermediate is too large for the GPU path";
+    deep_why(p, "PNG: 16-bit resize whose f32 intermediate is too large for the GPU path",
+             "TIFF: 16-bit resize whose f32 intermediate is too large for the GPU path");
     return false;
   }
   return true;
@@ -1112,14 +1122,15 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     C = (uint32_t)p.bmp.out_c;
   } else if (opt_.tiff && is_tiff(h, len)) {  // option "tiff"
     p.fmt = kFmtTiff;
-    parse_tiff_header(h, len, p.tiff, opt_.tiff_deflate);  // option "tiff_deflate" admits compression 8 / 32946
+    // option "tiff_deflate" admits compression 8 / 32946, option "tiff16" 16-bit samples
+    parse_tiff_header(h, len, p.tiff, opt_.tiff_deflate, opt_.tiff16);
     if (p.tiff.status != TH_OK) {
       p.status = p.tiff.status == TH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
       return DG_OK;
     }
     // the limits of the BMP path: the pixel buffer and the file stay 32-bit addressable (the decoded arena
     // is held under 2^31 by the header walk)
-    if ((uint64_t)p.tiff.width * p.tiff.height * 4ull >= (1ull << 31) || len >= (1ull << 28)) {
+    if ((uint64_t)p.tiff.width * p.tiff.height * 4ull * (p.tiff.bits / 8) >= (1ull << 31) || len >= (1ull << 28)) {
       p.tiff.status = TH_UNSUPPORTED;
       p.tiff.why = "TIFF: image too large for the GPU path";
       p.status = DG_ERR_UNSUPPORTED;
@@ -1194,7 +1205,8 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     }
   }
   p.channels = (int32_t)C;  // pre-transform (image_processing.rs:349-351)
-  const bool deep = p.fmt == kFmtPng && p.png.depth == 16;  // option "png16" (parse_png_header refuses them without)
+  // 16-bit samples: a PNG's (option "png16") or a TIFF's (option "tiff16"); the header walks refuse them without
+  const bool deep = (p.fmt == kFmtPng && p.png.depth == 16) || (p.fmt == kFmtTiff && p.tiff.bits == 16);
   p.bit_depth = deep && !cfg_.image_to_rgb8 ? 16 : 8;       // to_rgb8 (:367-372) leaves Rgb8
   uint32_t ow = W, oh = H;
   if (has_cfg_) {
@@ -1219,7 +1231,8 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     // the reference resizes non-U8 pixel types with image's own f32 Lanczos3
     // (resize_to_fill), not the fast_image_resize path restated here
     if (!opt_.resize16) {
-      p.png.why = "PNG: 16-bit resize (only a 16-bit image of its bucket's size decodes on the GPU)";
+      deep_why(p, "PNG: 16-bit resize (only a 16-bit image of its bucket's size decodes on the GPU)",
+               "TIFF: 16-bit resize (only a 16-bit image of its bucket's size decodes on the GPU; option \"resize16\")");
       p.status = DG_ERR_UNSUPPORTED;
       return DG_OK;
     }
@@ -1230,12 +1243,14 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
   }
   const bool deep_enc = deep && cfg_.pre_encode_images && !cfg_.image_to_rgb8;  // 16-bit samples at an encoder
   if (deep_enc && !opt_.penc16) {
-    p.png.why = "PNG: 16-bit image to an encoder (the GPU encoders take 8-bit samples)";
+    deep_why(p, "PNG: 16-bit image to an encoder (the GPU encoders take 8-bit samples)",
+             "TIFF: 16-bit image to an encoder (the GPU encoders take 8-bit samples; option \"penc16\")");
     p.status = DG_ERR_UNSUPPORTED;
     return DG_OK;
   }
   if (deep_enc && cfg_.encode_format != 0) {  // image 0.25's JpegEncoder rejects 16-bit colour types: the reference drops the sample
-    p.png.why = "PNG: 16-bit image to the JPEG encoder (it takes 8-bit samples only; option \"penc16\" covers encode_format png)";
+    deep_why(p, "PNG: 16-bit image to the JPEG encoder (it takes 8-bit samples only; option \"penc16\" covers encode_format png)",
+             "TIFF: 16-bit image to the JPEG encoder (it takes 8-bit samples only; option \"penc16\" covers encode_format png)");
     p.status = DG_ERR_UNSUPPORTED;
     return DG_OK;
   }
@@ -1532,7 +1547,10 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   if (next()) return DG_ERR_DEVICE;
   if (!from_fix && b.any_gif) launch_gif_expand(sl.st, dm, lst(L_GIF_EXPAND), cnt(L_GIF_EXPAND));
   if (!from_fix && b.any_bmp) launch_bmp_expand(sl.st, dm, lst(L_BMP_EXPAND), cnt(L_BMP_EXPAND));
-  if (!from_fix && b.any_tiff) launch_tiff_expand(sl.st, dm, lst(L_TIFF_EXPAND), cnt(L_TIFF_EXPAND));
+  if (!from_fix && b.any_tiff) {
+    launch_tiff_expand(sl.st, dm, lst(L_TIFF_EXPAND), cnt(L_TIFF_EXPAND));
+    launch_tiff_expand16(sl.st, dm, lst(L_TIFF_EXPAND16), cnt(L_TIFF_EXPAND16));  // (option "tiff16")
+  }
   if (!from_fix && b.any_webp) launch_vp8l_store(sl.st, dm, lst(L_VP8L_STORE), cnt(L_VP8L_STORE));
   if (!from_fix && b.any_vp8) launch_vp8_rgb(sl.st, dm, lst(L_VP8_RGB), cnt(L_VP8_RGB));
   if (!from_fix && b.any_png) {
@@ -1641,7 +1659,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   launch_resize_hb(sl.st, dd, lst(L_RH0), b.hclass[0], 0, opt_.h_prefetch, opt_.h_planar, b.h_zune != 0);
   launch_resize_hv(sl.st, dd, lst(L_RHV), b.hvclass);
   launch_resize_h(sl.st, dd, lst(L_RHX0), cnt(L_RHX0), 0 | ((opt_.debug_flags & 0xFF) << 8));
-  if (!from_fix) launch_r16_v(sl.st, dd, lst(L_R16V), cnt(L_R16V));  // (PNG only: nothing a resync round redoes)
+  if (!from_fix) launch_r16_v(sl.st, dd, lst(L_R16V), cnt(L_R16V));  // (PNG and TIFF only: nothing a resync round redoes)
   if (next()) return DG_ERR_DEVICE;
   launch_resize_v(sl.st, dd, lst(L_RV1), cnt(L_RV1), 1, opt_.v_units);
   launch_resize_vt(sl.st, dd, lst(L_RVT1), cnt(L_RVT1), 1, b.v_tile);

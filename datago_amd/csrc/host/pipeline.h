@@ -56,7 +56,7 @@ struct ImagePlan {
   bool enc_la_gray = false;  // resized LA: encoded as the GrayImage over its bytes
   uint64_t img_bytes = 0;  // transformed image bytes (out_w * out_h * out_c, x 2 at bit_depth 16)
   // 16-bit resize (option "resize16", dg_resize16.h): the image crate's resize_to_fill
-  bool r16 = false;          // a 16-bit PNG that is not its bucket's size
+  bool r16 = false;          // a 16-bit PNG or TIFF that is not its bucket's size
   bool r16_passes = false;   // ... and whose intermediate differs from the source (else a pure crop)
   R16Geom r16g = {0, 0, 0, 0};
   uint32_t r16_s0 = 0, r16_ns = 0;  // samples of a decoded row the intermediate holds: first, count (x 4)
@@ -226,6 +226,7 @@ enum ListId {
   L_BMP_RLE, L_BMP_EXPAND,                                  // BMP decode (dg_bmp.hip): per RLE image, per 64 groups of 4 pixels
   L_TIFF_LZW, L_TIFF_PACKBITS, L_TIFF_EXPAND,               // TIFF decode (dg_tiff.hip): per LZW / PackBits segment, per 4 row pieces
   L_TIFF_INFLATE,                                           // TIFF Deflate (dg_tiff_inflate.hip): per Deflate segment
+  L_TIFF_EXPAND16,                                          // 16-bit TIFF (k_tiff_expand16): per 4 row pieces
   L_COUNT
 };
 static_assert((int)L_COUNT <= 64, "Batch::lists");

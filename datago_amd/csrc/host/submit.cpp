@@ -715,7 +715,8 @@ void Context::layout_bmp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, 
 
 // A TIFF (option "tiff"): the segments are read in place; the decoded arena of a compressed file (every
 // segment's bytes, each slot a multiple of 16), the segment table in the blob and the L8 / La8 / Rgb8 / Rgba8
-// pixels, which then are what an 8-bit PNG's pixels are.
+// pixels, which then are what an 8-bit PNG's pixels are.  16-bit samples (option "tiff16"): two bytes per sample in
+// the arena and in the pixel plane, whose rows of native-endian uint16 are what k_png_expand16 leaves of a 16-bit PNG.
 void Context::layout_tiff(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
   const TiffHeader &g = b.plans[i].tiff;
   d.fmt = kFmtTiff;
@@ -731,8 +732,11 @@ void Context::layout_tiff(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl,
   td.seg_w = g.seg_w;
   td.seg_h = g.seg_h;
   td.across = g.across;
+  td.bits = (uint32_t)g.bits;
+  td.swap = (uint32_t)g.swap;
+  d.sample_bytes = g.bits == 16 ? 2 : 1;
   if (g.compression != TIFF_NONE) o.raw = bl.L.take((size_t)g.dec_total + 64, 256);
-  d.pix_stride = (uint32_t)align_up((size_t)g.width * d.dec_c, 16);
+  d.pix_stride = (uint32_t)align_up((size_t)g.width * d.dec_c * d.sample_bytes, 16);
   o.pix = bl.late().take((size_t)d.pix_stride * g.height);
   o.late |= bl.alias ? 2u : 0u;
   static_assert(sizeof(TiffSegment) == sizeof(TiffSeg), "the segment table is uploaded as it is");
@@ -962,7 +966,7 @@ int Context::plan_resize(const ImagePlan &p, Batch &b, BatchLayout &bl, ImageDes
   d.out_h = p.out_h;
   d.out_c = p.out_c;
   d.out_stride = p.out_w * p.out_c * (p.bit_depth == 16 ? 2 : 1);
-  if (p.r16) return plan_resize16(p, bl, d, o);  // 16-bit PNG (option "resize16"): the image crate's f32 passes
+  if (p.r16) return plan_resize16(p, bl, d, o);  // 16-bit PNG or TIFF (option "resize16"): the image crate's f32 passes
   uint32_t cw = W, chh = H;     // extent of the current image's valid window
   uint32_t xoff = 0, yoff = 0;  // window origin (pixels, rows) inside the current buffer
   int last_stage = -1;
@@ -1092,7 +1096,7 @@ int Context::plan_resize(const ImagePlan &p, Batch &b, BatchLayout &bl, ImageDes
   return last_stage;
 }
 
-// The passes of a 16-bit PNG that is not its bucket's size (dg_resize16.h):
+// The passes of a 16-bit PNG or TIFF that is not its bucket's size (dg_resize16.h):
 // pass[0] = the vertical pass into the f32 intermediate, pass[1] = the
 // horizontal pass; the integer centre crop folds into both (out0, and the
 // sample window [r16_s0, + r16_ns) of the intermediate's rows).  The tap
@@ -1742,7 +1746,7 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
   } else if (d.fmt == kFmtTiff) {
     const ListId dec = d.tiff.comp == TIFF_LZW ? L_TIFF_LZW : d.tiff.comp == TIFF_DEFLATE ? L_TIFF_INFLATE : L_TIFF_PACKBITS;
     for (uint32_t sg = 0; d.tiff.comp != TIFF_NONE && sg < d.tiff.nseg; sg++) b.lists[dec].push_back({I, sg});
-    for (uint32_t it = 0; it < d.height * d.tiff.across; it += kTiffExpandPieces) b.lists[L_TIFF_EXPAND].push_back({I, it});
+    for (uint32_t it = 0; it < d.height * d.tiff.across; it += kTiffExpandPieces) b.lists[d.tiff.bits == 16 ? L_TIFF_EXPAND16 : L_TIFF_EXPAND].push_back({I, it});
   } else if (d.fmt == kFmtBmp) {
     if (d.bmp.rle) b.lists[L_BMP_RLE].push_back({I, 0});
     for (uint32_t it = 0; it < bmp_row_groups(d.width) * d.height; it += 64) b.lists[L_BMP_EXPAND].push_back({I, it});

@@ -41,7 +41,7 @@ struct Entry {
 };
 }  // namespace
 
-void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate) {
+void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate, bool deep) {
   h = TiffHeader();
   if (!is_tiff(d, n)) return fail(h, TH_CORRUPT, "not a TIFF");
   const Reader r{d, n, d[0] == 'M'};
@@ -82,12 +82,19 @@ void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate) 
   if (spp == 0 || spp > 4) return fail(h, TH_UNSUPPORTED, "TIFF: more than four samples per pixel");
   if (e[T_BITS].present && e[T_BITS].count != spp && !(e[T_BITS].count == 1 && spp == 1))
     return fail(h, TH_UNSUPPORTED, "TIFF: BitsPerSample count differs from SamplesPerPixel");
-  for (uint32_t k = 0; k < spp; k++)
-    if ((e[T_BITS].present ? e[T_BITS].get(r, k) : 1u) != 8u) return fail(h, TH_UNSUPPORTED, "TIFF: samples not 8 bits");
+  const uint32_t bits = e[T_BITS].present ? e[T_BITS].get(r, 0) : 1u;
+  for (uint32_t k = 0; k < spp; k++) {
+    const uint32_t b = e[T_BITS].present ? e[T_BITS].get(r, k) : 1u;
+    if (b != 8u && !(deep && b == 16u)) return fail(h, TH_UNSUPPORTED, "TIFF: samples not 8 bits");
+    if (b != bits) return fail(h, TH_UNSUPPORTED, "TIFF: mixed BitsPerSample");  // (deep only: 8 and 16 in one pixel)
+  }
+  const uint32_t sb = bits / 8u;  // bytes per sample
   if (e[T_FMT].present)
     for (uint32_t k = 0; k < e[T_FMT].count; k++)
       if (e[T_FMT].get(r, k) != 1u) return fail(h, TH_UNSUPPORTED, "TIFF: signed or float samples");
   if (photo > 2) return fail(h, TH_UNSUPPORTED, "TIFF: palette, mask, CMYK, YCbCr or CIELab photometric");
+  // libtiff (Pillow) returns the stored samples, the tiff crate inverts them
+  if (photo == 0 && bits == 16u) return fail(h, TH_UNSUPPORTED, "TIFF: 16-bit WhiteIsZero");
   if (one(T_PLANAR, 1) != 1) return fail(h, TH_UNSUPPORTED, "TIFF: PlanarConfiguration 2");
   if (one(T_FILL, 1) != 1) return fail(h, TH_UNSUPPORTED, "TIFF: FillOrder 2");
   if (pred == 3) return fail(h, TH_UNSUPPORTED, "TIFF: floating-point predictor");
@@ -111,8 +118,10 @@ void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate) 
   h.compression = (int)comp;
   h.predictor = (int)pred;
   h.invert = photo == 0;
+  h.bits = (int)bits;
+  h.swap = bits == 16u && r.be;
   // image's default Limits::max_alloc (512 MiB) covers the decoded image
-  if ((uint64_t)h.width * h.height * spp > (512ull << 20)) return fail(h, TH_UNSUPPORTED, "TIFF: image over image's allocation limit");
+  if ((uint64_t)h.width * h.height * spp * sb > (512ull << 20)) return fail(h, TH_UNSUPPORTED, "TIFF: image over image's allocation limit");
   // ---- the segments
   h.tiled = e[T_TW].present || e[T_TOFF].present;
   const Entry &eo = e[h.tiled ? T_TOFF : T_SOFF], &ec = e[h.tiled ? T_TCNT : T_SCNT];
@@ -122,7 +131,7 @@ void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate) 
     h.seg_h = one(T_TH, 0);
     if (h.seg_w == 0 || h.seg_h == 0) return fail(h, TH_CORRUPT, "TIFF: tile size missing");
     if (h.seg_w % 16 || h.seg_h % 16) return fail(h, TH_UNSUPPORTED, "TIFF: tile size not a multiple of 16");
-    if ((uint64_t)h.seg_w * h.seg_h * spp >= (1ull << 31)) return fail(h, TH_UNSUPPORTED, "TIFF: tile too large for the GPU path");
+    if ((uint64_t)h.seg_w * h.seg_h * spp * sb >= (1ull << 31)) return fail(h, TH_UNSUPPORTED, "TIFF: tile too large for the GPU path");
   } else {
     const uint32_t rps = one(T_RPS, 0xFFFFFFFFu);
     if (rps == 0) return fail(h, TH_CORRUPT, "TIFF: RowsPerStrip 0");
@@ -134,7 +143,7 @@ void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate) 
   const uint64_t nseg = (uint64_t)h.across * h.down;
   if (eo.count != nseg || ec.count != nseg) return fail(h, TH_CORRUPT, "TIFF: segment table does not fit the image");
   h.segs.resize((size_t)nseg);
-  const uint64_t rowb = (uint64_t)h.seg_w * spp;
+  const uint64_t rowb = (uint64_t)h.seg_w * spp * sb;
   for (uint32_t s = 0; s < nseg; s++) {
     TiffSegment &g = h.segs[s];
     g.off = eo.get(r, s);

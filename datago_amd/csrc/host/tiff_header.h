@@ -20,7 +20,7 @@ enum TiffCompression { TIFF_NONE = 1, TIFF_LZW = 5, TIFF_DEFLATE = 8, TIFF_PACKB
 // One strip or tile (the layout of TiffSeg, dg_types.h).
 struct TiffSegment {
   uint32_t off, nbytes;  // the coded bytes in the file
-  uint32_t dec;          // bytes they decode to
+  uint32_t dec;          // bytes they decode to (rows x segment width x samples x bytes per sample)
   uint32_t dst;          // where those lie in the image's decoded arena (a multiple of 16)
 };
 
@@ -32,6 +32,8 @@ struct TiffHeader {
   int compression = 0;     // TIFF_*
   int predictor = 1;       // 1 or 2
   int invert = 0;          // WhiteIsZero
+  int bits = 8;            // BitsPerSample of every sample: 8, or 16 (L16 / La16 / Rgb16 / Rgba16; only with `deep`)
+  int swap = 0;            // 16-bit samples of an MM file: big-endian in the segments' decoded bytes
   int tiled = 0;
   uint32_t seg_w = 0, seg_h = 0;    // the tile, or width x RowsPerStrip (at most the height)
   uint32_t across = 0, down = 0;    // segments per row of segments (1 for strips) and rows of them
@@ -41,6 +43,9 @@ struct TiffHeader {
 
 bool is_tiff(const uint8_t *d, size_t n);
 // deflate (option "tiff_deflate"): compression 8 and 32946 pass, with predictor 1 or 2; without it they are TH_UNSUPPORTED.
-void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate = false);
+// deep (option "tiff16"): BitsPerSample 16 for every sample passes, with the other rules unchanged (dec, dec_total and
+// the uncompressed length check count two bytes per sample); 16-bit WhiteIsZero is TH_UNSUPPORTED.  Without it
+// such a file is TH_UNSUPPORTED "TIFF: samples not 8 bits".
+void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate = false, bool deep = false);
 
 }  // namespace dg

@@ -401,6 +401,19 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 differs, where the final block ends at the segment's last byte and the four bytes are
  *                 there.  Distances are not held to the header's window size (zlib does not either).  Any
  *                 other value: DG_ERR_INVALID
+ *   "tiff16"   1 = with "tiff" (alone it changes nothing), a TIFF whose samples all have 16 bits
+ *                 (SampleFormat absent or 1, either byte order) decodes as well: L16 / La16 / Rgb16 /
+ *                 Rgba16 as native-endian uint16, top row first, with bit_depth 16 and channels 1 to 4, or
+ *                 Rgb8 under image_to_rgb8 by a 16-bit PNG's conversion (default 0: such a file stays
+ *                 DG_ERR_UNSUPPORTED "TIFF: samples not 8 bits").  Compression, predictor 2 (on whole
+ *                 samples, modulo 65536), strips, tiles and ExtraSamples follow the rules of "tiff" (Deflate
+ *                 needs "tiff_deflate").  From the pixel plane on it is a 16-bit PNG's pixels: of its
+ *                 bucket's size it needs nothing more, otherwise "resize16", into the PNG encoder "penc16";
+ *                 into the JPEG encoder it is DG_ERR_UNSUPPORTED.  Also DG_ERR_UNSUPPORTED, each with a
+ *                 text that begins "TIFF: ": 16-bit WhiteIsZero (libtiff and the tiff crate disagree),
+ *                 mixed BitsPerSample, and an image of width * height * 8 bytes at or over 2^31.  Gray +
+ *                 alpha at 16 bits rests on the tiff crate's source alone (libtiff under Pillow does not
+ *                 open it).  Any other value: DG_ERR_INVALID
  *   "webp"     1 = decode still lossless WebP files on the GPU: a RIFF/WEBP file whose image data is a
  *                 VP8L chunk, alone (simple file) or behind VP8X with ICCP / EXIF / XMP / unknown chunks
  *                 skipped (default 0: DG_ERR_CORRUPT from every entry point, like any format the library

@@ -10,6 +10,15 @@ images, repeated) written by Pillow (libtiff: 74 strips of 21 rows) as
     deflate_pred  Adobe Deflate with predictor 2
     png        the same pixels as an RGB PNG: the nearest existing GPU path
 
+With --deep, the 16-bit legs instead (option "tiff16"; samples = the pool's 8-bit ones x 257):
+
+    gray16_lzw_pred  16-bit gray, LZW with predictor 2, written by Pillow (strips of 32 rows)
+    rgb16_raw        16-bit RGB, uncompressed, MM byte order, one strip (Pillow writes no 16-bit colour, and
+                     the tests' LZW writer is too slow for files of this size)
+    gray16_png, rgb16_png   the same pixels as 16-bit PNGs (options "png16", "resize16")
+
+Pillow's leg there is gray only (decode, to float, Lanczos resize): it holds no 16-bit colour.
+
 and sent through dg_submit_device, device-resident input and output, by one
 context (crop_and_resize to the 512 / 16 buckets).  Per pool: ms per batch with
 one batch in flight (median), the pipelined rate with three in flight and the
@@ -38,6 +47,7 @@ from bmp_rate import pillow_rate  # noqa: E402  (the same 16-process Pillow leg)
 W, H = 1024, 1536
 KINDS = ("raw", "lzw", "lzw_pred", "deflate", "deflate_pred", "png")
 TIFFS = KINDS[:5]
+KINDS16 = ("gray16_lzw_pred", "rgb16_raw", "gray16_png", "rgb16_png")
 
 
 def make_pool(distinct: int):
@@ -55,6 +65,40 @@ def make_pool(distinct: int):
             im.save(buf, **kw)
             pool[kind].append(buf.getvalue())
     return pool
+
+
+def make_pool16(distinct: int):
+    from PIL import Image
+    from datago_amd import synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import tiff16_craft
+    pool = {k: [] for k in KINDS16}
+    for i in range(distinct):
+        px = synth.synth_pixels(np.random.default_rng(900 + i), W, H, False).astype(np.uint16) * 257
+        for kind, kw in (("gray16_lzw_pred", dict(format="TIFF", compression="tiff_lzw", tiffinfo={317: 2})), ("gray16_png", dict(format="PNG"))):
+            buf = io.BytesIO()
+            Image.fromarray(px[:, :, 1]).save(buf, **kw)
+            pool[kind].append(buf.getvalue())
+        pool["rgb16_raw"].append(tiff16_craft.tiff16("", px, be=True)[1])
+        pool["rgb16_png"].append(synth.encode_png16(px, 2, np.random.default_rng(i)))
+    return pool
+
+
+def _pillow16_one(job):
+    from PIL import Image
+    data, size = job
+    return len(Image.open(io.BytesIO(data)).convert("F").resize(size, Image.LANCZOS).tobytes())
+
+
+def pillow16_rate(files, size, procs: int, passes: int = 3):
+    import multiprocessing as mp
+    jobs, secs = [(f, size) for f in files], []
+    with mp.get_context("fork").Pool(procs) as pool:
+        for k in range(passes + 1):  # the first pass warms the workers
+            t0 = time.perf_counter()
+            pool.map(_pillow16_one, jobs, chunksize=4)
+            secs.append(time.perf_counter() - t0)
+    return {"procs": procs, "files": len(files), "passes": passes, "images_per_s": round(len(files) / statistics.median(secs[1:]), 1)}
 
 
 def run(ctx, L, files, steps: int, warmup: int, depth: int = 3):
@@ -119,25 +163,28 @@ def main() -> int:
     ap.add_argument("--procs", type=int, default=16)
     ap.add_argument("--no-pillow", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--deep", action="store_true", help="the 16-bit legs (option tiff16) instead")
     a = ap.parse_args()
-    pool = make_pool(a.distinct)
+    kinds, tiffs = (KINDS16, KINDS16[:2]) if a.deep else (KINDS, TIFFS)
+    pool = make_pool16(a.distinct) if a.deep else make_pool(a.distinct)
     res = {"images": a.n, "distinct": a.distinct, "size": [W, H], "coded_bytes": {k: len(v[0]) for k, v in pool.items()}}
     from oracle import buckets as B
     size = B.ARAwareTransform(512, 16, 0.5, 2.0).target_size(W, H)
     res["bucket"] = list(size)
     if not a.no_pillow:  # first: forked workers, before this process opens the GPU
-        res["pillow"] = {k: pillow_rate([pool[k][i % a.distinct] for i in range(a.n)], size, a.procs) for k in TIFFS}
+        res["pillow"] = {k: (pillow16_rate if a.deep else pillow_rate)([pool[k][i % a.distinct] for i in range(a.n)], size, a.procs)
+                         for k in tiffs[:1 if a.deep else None]}
     from datago_amd import _lib as L
     kw = dict(crop_and_resize=True, default_image_size=512, downsampling_ratio=16, min_aspect_ratio=0.5,
               max_aspect_ratio=2.0)
-    for kind in KINDS:
-        ctx = L.Context(0, tiff=True, tiff_deflate=True, **kw)
+    for kind in kinds:
+        ctx = L.Context(0, tiff=True, tiff_deflate=True, tiff16=a.deep, png16=a.deep, resize16=a.deep, **kw)
         res[kind] = run(ctx, L, [pool[kind][i % a.distinct] for i in range(a.n)], a.steps, a.warmup)
         ctx.close()
     r = lambda k: res[k]["images_per_s_pipelined"]  # noqa: E731
-    for kind in TIFFS:
-        res["%s_over_png" % kind] = round(r(kind) / r("png"), 3)
-        if not a.no_pillow:
+    for kind in tiffs:
+        res["%s_over_png" % kind] = round(r(kind) / r(kind[:kind.index("_")] + "_png" if a.deep else "png"), 3)
+        if not a.no_pillow and kind in res["pillow"]:
             res["%s_over_pillow" % kind] = round(r(kind) / res["pillow"][kind]["images_per_s"], 2)
     print(json.dumps(res))
     if a.out:
