@@ -6,7 +6,8 @@ bases, inflate chunk and unfilter flag numbers, blob offsets of palettes and
 encoder headers, the shift of the aliased late region, the walk over the
 planned images that skips the failed ones -- must not leak into an image's
 result.  The comparison is bytes to bytes against the same library, through
-the host path and the device-pointer path: no tolerance."""
+the host path and the device-pointer path: no tolerance.
+test_gpu_all_formats.py does the same for the formats this corpus does not hold (GIF, WebP, BMP, TIFF, the JPEG forms)."""
 import numpy as np
 import pytest
 
