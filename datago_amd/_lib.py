@@ -335,7 +335,7 @@ class Context:
                  resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False,
                  jenc_optimize: bool = False, gif: bool = False, webp: bool = False, webp_lossy: bool = False,
                  webp_alpha: bool = False, bmp: bool = False, tiff: bool = False, tiff_deflate: bool = False,
-                 tiff16: bool = False):
+                 tiff16: bool = False, penc_match: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -356,6 +356,7 @@ class Context:
                 # ... and re-encode as bit-depth-16 PNGs under pre_encode_images with encode_format png
                 ("penc16", penc16),
                 ("penc_dynamic", penc_dynamic),  # PNG re-encode: per-image Huffman codes where they make the file shorter
+                ("penc_match", penc_match),  # PNG re-encode: LZ77 matches where they make the file shorter
                 ("jenc_optimize", jenc_optimize),  # JPEG re-encode: per-image Huffman tables (libjpeg's optimize_coding rule)
                 # GIF files: the first frame on the logical screen as RGBA8; off: DG_ERR_CORRUPT like any unknown format
                 ("gif", gif),

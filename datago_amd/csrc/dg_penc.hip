@@ -16,6 +16,10 @@
 //   k_penc_tree     one workgroup per image: per-image Huffman code, block
 //                   header, dynamic block or fixed (dg_penc_tree.h)
 //   k_penc_count_dyn  piece bit lengths under the image's code ]
+//   [option "penc_match": k_penc_match parses every piece again with LZ77
+//   matches into a token buffer, k_penc_mtree chooses per image among the
+//   parent's blocks and the match tokens', k_penc_mcount / k_penc_mwrite code
+//   the tokens of the images that took them ("matches" below) ]
 //   k_enc_scan     (dg_enc.hip) exclusive scan of the piece bit lengths
 //   k_penc_write   one thread per piece: the codes OR-ed LSB-first into the
 //                  zeroed bit buffer at the piece's offset
@@ -312,13 +316,15 @@ __global__ __launch_bounds__(256) void k_penc_tree(ImageDesc *__restrict__ imgs,
 
 // Second pass over the pieces of the images that took the dynamic block:
 // their bit lengths under the image's table (k_enc_scan turns them into offsets).
+// MATCH (option "penc_match"): an image that took the match tokens (e.mode) is k_penc_mcount's.
+template <bool MATCH>
 __global__ __launch_bounds__(256) void k_penc_count_dyn(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
   __shared__ uint32_t tab[kPtTableWords];
   const WgItem it = list[blockIdx.x];
   const ImageDesc &im = imgs[it.image];
   if (im.status) return;
   const EncDesc &e = im.enc;
-  if (!e.dyn) return;
+  if (!e.dyn || (MATCH && e.mode)) return;
   const DG_GLOBAL uint32_t *gt = gp<const uint32_t>(e.tab);
   for (uint32_t i = threadIdx.x; i < kPtTableWords; i += 256) tab[i] = gt[i];
   __syncthreads();
@@ -336,13 +342,15 @@ __global__ __launch_bounds__(256) void k_penc_count_dyn(const ImageDesc *__restr
 // DYN (option "penc_dynamic"): an image that took the dynamic block packs its
 // tokens under its table (in LDS), from bit hdr_bits on, and its last piece
 // appends the end-of-block code (the fixed one is seven zero bits: nothing to write).
-template <bool DYN>
+// MATCH (option "penc_match"): an image that took the match tokens (e.mode) is k_penc_mwrite's.
+template <bool DYN, bool MATCH>
 __global__ __launch_bounds__(256) void k_penc_write(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
   __shared__ uint32_t tab[DYN ? kPtTableWords : 1];
   const WgItem it = list[blockIdx.x];
   const ImageDesc &im = imgs[it.image];
   if (im.status) return;
   const EncDesc &e = im.enc;
+  if (MATCH && e.mode) return;
   const bool dyn = DYN && e.dyn;  // (uniform: a workgroup belongs to one image)
   if (DYN && dyn) {
     const DG_GLOBAL uint32_t *gt = gp<const uint32_t>(e.tab);
@@ -377,6 +385,335 @@ __global__ __launch_bounds__(256) void k_penc_write(const ImageDesc *__restrict_
   }
   if (nacc) atomicOr((uint32_t *)&w[wi], (uint32_t)acc);
   if (pc == 0 && !dyn) atomicOr((uint32_t *)&w[0], 3u);  // BFINAL = 1, BTYPE = 01 (fixed Huffman)
+}
+
+// ------------------------------------------------------------ matches (option "penc_match")
+//
+// DESIGN.md "Matches (option penc_match)" states the parse; tests/ref_penc_match.py
+// restates it.  One wave per 1 KiB piece:
+//   k_penc_match   window + piece (8 KiB) into LDS as dwords; a 4096-entry hash
+//                  table beside it (atomicMax: the latest position wins, in any
+//                  order); the piece in groups of 64 positions, one per lane:
+//                  look up, meet, insert, then each lane extends its near and
+//                  far candidates with dword compares out of LDS; the greedy
+//                  chain by pointer doubling over next[p] (10 rounds, not 1,024
+//                  steps); the chain's tokens compacted, 16 positions per lane,
+//                  into the token buffer: a literal byte, or length << 16 |
+//                  distance; the piece's bits under the fixed code, its token
+//                  count, both histograms
+//   k_penc_mtree   one workgroup per image: the parent's block(s) as k_penc_tree
+//                  builds them, the match tokens' (pm_build), the choice
+//   k_penc_mcount  piece bits of an image that took the match tokens: the fixed
+//                  count kept, or the tokens under the image's two tables
+//   k_penc_mwrite  the tokens' codes: a lane takes a run of tokens, a wave scan
+//                  gives it its bit offset
+// An image that keeps the parent's tokens goes through the parent's kernels.
+
+constexpr uint32_t kPmWindow = 7168, kPmSpan = kPmWindow + kPencPiece, kPmHashBits = 12;
+static_assert(kPencMatchTabBytes >= kPmTableWords * 4, "the histogram / code table region with matches");
+static_assert(kPencMatchPieceBytes == 8 + 4 * kPencPiece, "two counters and a token word per byte");
+
+struct MatchSmem {
+  uint32_t buf[kPmSpan / 4 + 2];      // stream bytes [ws, p1 + 3), and a dword for the unaligned read of the last
+  uint32_t tab[1u << kPmHashBits];    // hash -> 1 + offset in buf of the largest inserted position; 0: none
+  uint32_t best[kPencPiece];          // per piece position: length << 16 | distance; 0: a literal
+  uint16_t jump[2][kPencPiece + 2];   // next[p] and its powers; the piece's length is the chain's end
+  uint8_t on[kPencPiece + 4];         // the position is on the greedy chain
+  uint32_t hist[kPtTableWords + 32];  // literal/length counts, then distance counts
+};
+
+// four bytes at any byte offset of buf
+__device__ __forceinline__ uint32_t lds_le32(const uint32_t *buf, uint32_t at) {
+  return __builtin_amdgcn_alignbyte(buf[(at >> 2) + 1], buf[at >> 2], at & 3u);
+}
+__device__ __forceinline__ uint32_t pm_hash(uint32_t v) { return (v * 0x9E3779B1u) >> (32 - kPmHashBits); }
+
+// how many of the lim bytes at a equal those at b (bytes past the loaded ones may differ or not: clamped)
+__device__ __forceinline__ uint32_t pm_common(const uint32_t *buf, uint32_t a, uint32_t b, uint32_t lim) {
+  uint32_t k = 0;
+  while (k < lim) {
+    const uint32_t x = lds_le32(buf, a + k) ^ lds_le32(buf, b + k);
+    if (x) {
+      k += (uint32_t)__builtin_ctz(x) >> 3;
+      break;
+    }
+    k += 4;
+  }
+  return min(k, lim);
+}
+
+// A token word's codes: tabs = the image's literal/length table (distance table kPmDistAt - kPmLitAt words on), or
+// nullptr for the fixed code.  Every emit is of 15 bits at the most.
+template <class Emit>
+__device__ __forceinline__ void pm_token(uint32_t word, const DG_GLOBAL uint32_t *tabs, Emit emit) {
+  uint32_t sym = word, eb = 0, ev = 0, code, len;
+  if (word >> 16) len_code(word >> 16, sym, eb, ev);
+  if (tabs) {
+    code = tabs[sym] & 0xFFFFu;
+    len = tabs[sym] >> 16;
+  } else {
+    fixed_code(sym, code, len);
+  }
+  emit(code, len);
+  if (!(word >> 16)) return;
+  if (eb) emit(ev, eb);
+  pm_dist_code(word & 0xFFFFu, sym, eb, ev);
+  if (tabs)
+    emit(tabs[kPmDistAt - kPmLitAt + sym] & 0xFFFFu, tabs[kPmDistAt - kPmLitAt + sym] >> 16);
+  else
+    emit(__builtin_bitreverse32(sym) >> 27, 5u);
+  if (eb) emit(ev, eb);
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_scan_excl(uint32_t v, uint32_t lane) {
+  uint32_t inc = v;
+  for (uint32_t o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += t;
+  }
+  return inc - v;
+}
+
+__global__ __launch_bounds__(64) void k_penc_match(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  __shared__ MatchSmem sm;
+  const WgItem it = list[blockIdx.x];
+  const ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  const EncDesc &e = im.enc;
+  if (!e.jopt || !e.tab) return;
+  const uint32_t pc = it.item0, lane = threadIdx.x;
+  const uint32_t N = e.h * (e.w * e.C + 1);
+  const uint32_t p0 = pc * kPencPiece, p1 = min(p0 + kPencPiece, N), ws = p0 > kPmWindow ? p0 - kPmWindow : 0;
+  const uint32_t L = p1 - p0, base = p0 - ws;  // piece position j stands at byte base + j of buf
+  // ws is a multiple of 1 KiB and the stream 256-byte aligned: dword loads; the stream's buffer has 16 spare bytes
+  const DG_GLOBAL uint32_t *src = gp<const uint32_t>(e.coef + ws);
+  const uint32_t nload = (min(p1 + 3, N) - ws + 3) / 4;  // <= kPmSpan / 4 + 1
+  for (uint32_t i = lane; i < nload; i += 64) sm.buf[i] = src[i];
+  for (uint32_t i = lane; i < (1u << kPmHashBits); i += 64) sm.tab[i] = 0;
+  for (uint32_t i = lane; i < kPtTableWords + 32; i += 64) sm.hist[i] = 0;
+  for (uint32_t i = lane; i < kPencPiece + 4; i += 64) sm.on[i] = 0;
+  __syncthreads();
+  for (uint32_t q = lane; q < base; q += 64)  // the window: H(q) exists where q + 3 < N
+    if (ws + q + 3 < N) atomicMax(&sm.tab[pm_hash(lds_le32(sm.buf, q))], q + 1);
+  __syncthreads();
+  const uint32_t C = e.C;
+  for (uint32_t g = 0; g < L; g += 64) {  // (uniform bounds: every lane meets the barriers)
+    const uint32_t j = g + lane, at = base + j;
+    const bool hashed = j < L && p0 + j + 3 < N;
+    const uint32_t h = hashed ? pm_hash(lds_le32(sm.buf, at)) : 0u;
+    const uint32_t far = hashed ? sm.tab[h] : 0u;  // the latest position before this group
+    __syncthreads();
+    if (hashed) atomicMax(&sm.tab[h], at + 1);
+    if (j < L) {
+      const uint32_t lim = min(258u, L - j);
+      uint32_t k = 0, d = 0;
+      if (lim >= 3) {
+#pragma unroll
+        for (uint32_t n = 0; n < 3; n++) {  // 1, C, 2C ascending (C = 1: 1 twice, the second never longer)
+          const uint32_t dd = n == 0 ? 1u : n * C;
+          if (p0 + j >= dd) {
+            const uint32_t kk = pm_common(sm.buf, at, at - dd, lim);
+            if (kk >= 3 && kk > k) {
+              k = kk;
+              d = dd;
+            }
+          }
+        }
+        if (far) {
+          const uint32_t kk = pm_common(sm.buf, at, far - 1, lim);
+          if (kk >= 6 && kk >= k + 2) {
+            k = kk;
+            d = at - (far - 1);
+          }
+        }
+      }
+      sm.best[j] = k ? k << 16 | d : 0u;
+      sm.jump[0][j] = (uint16_t)(j + (k ? k : 1u));  // <= L: a match ends inside its piece
+    }
+    __syncthreads();
+  }
+  if (lane == 0) {
+    sm.jump[0][L] = (uint16_t)L;
+    sm.on[0] = 1;
+  }
+  __syncthreads();
+  // Greedy chain from position 0 by pointer doubling: after r rounds `on` holds the chain's first 2^r positions
+  // and jump[cur] is next^(2^r).  A position marked during a round is on the chain whichever lane sees it when.
+  uint32_t cur = 0;
+  for (uint32_t step = 1; step < L; step <<= 1) {
+    for (uint32_t j = lane; j <= L; j += 64) {
+      const uint32_t t = sm.jump[cur][j];
+      if (j < L && sm.on[j] && t < L) sm.on[t] = 1;
+      sm.jump[cur ^ 1][j] = sm.jump[cur][t];
+    }
+    cur ^= 1;
+    __syncthreads();
+  }
+  // Tokens in order: a lane takes 16 consecutive positions
+  uint32_t cnt = 0, bits = 0;
+  for (uint32_t j = 16 * lane; j < min(16 * lane + 16, L); j++) cnt += sm.on[j];
+  uint32_t off = wave_scan_excl(cnt, lane);
+  DG_GLOBAL uint32_t *reg = gp<uint32_t>(e.jopt);
+  DG_GLOBAL uint32_t *tok = reg + 2 * (size_t)e.nblocks + (size_t)pc * kPencPiece;
+  for (uint32_t j = 16 * lane; j < min(16 * lane + 16, L); j++) {
+    if (!sm.on[j]) continue;
+    const uint32_t b = sm.best[j];
+    const uint32_t word = b ? b : (sm.buf[(base + j) >> 2] >> (8 * ((base + j) & 3u))) & 0xFFu;
+    tok[off++] = word;
+    pm_token(word, nullptr, [&](uint32_t, uint32_t n) { bits += n; });
+    if (b) {
+      uint32_t sym, eb, ev;
+      len_code(b >> 16, sym, eb, ev);
+      atomicAdd(&sm.hist[sym], 1u);
+      pm_dist_code(b & 0xFFFFu, sym, eb, ev);
+      atomicAdd(&sm.hist[kPtTableWords + sym], 1u);
+    } else {
+      atomicAdd(&sm.hist[word], 1u);
+    }
+  }
+  bits = wave_sum(bits);
+  cnt = wave_sum(cnt);
+  if (lane == 0) {
+    reg[pc] = bits;
+    reg[e.nblocks + pc] = cnt;
+  }
+  __syncthreads();
+  DG_GLOBAL uint32_t *gh = gp<uint32_t>(e.tab);
+  for (uint32_t i = lane; i < kPtTableWords + 32; i += 64)
+    if (sm.hist[i]) atomicAdd((uint32_t *)&gh[(i < kPtTableWords ? kPmLitAt : kPmDistAt - kPtTableWords) + i], sm.hist[i]);
+}
+
+struct MTreeSmem {
+  PtWork work;
+  PtOut po;
+  PmOut mo;
+  uint32_t f[kPtTableWords], fl[kPtTableWords], fd[32];
+  uint8_t seq[kPmSeq + 4];
+  uint64_t pfix, mfix;
+  uint32_t nmatch, which;
+};
+
+// One workgroup per image: the shortest in bits of the parent tokens under the fixed code, under their own code
+// (dynamic: option "penc_dynamic"), the match tokens under the fixed code and under their own codes; the earlier
+// on a tie.  Decide first, write second, as k_penc_tree.
+__global__ __launch_bounds__(256) void k_penc_mtree(ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list, bool dynamic) {
+  __shared__ MTreeSmem sm;
+  const WgItem it = list[blockIdx.x];
+  ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  EncDesc &e = im.enc;
+  if (!e.jopt || !e.tab) return;
+  const uint32_t t = threadIdx.x;
+  DG_GLOBAL uint32_t *tab = gp<uint32_t>(e.tab);
+  for (uint32_t i = t; i < kPtTableWords; i += 256) {
+    sm.f[i] = i < kPtLit ? tab[i] : 0u;
+    sm.fl[i] = i < kPtLit ? tab[kPmLitAt + i] : 0u;
+    if (i < 32) sm.fd[i] = i < kPmDist ? tab[kPmDistAt + i] : 0u;
+  }
+  __syncthreads();
+  if (t == 0) {
+    sm.f[256] = sm.fl[256] = 1;  // the end-of-block
+    uint32_t nm = 0, runs = 0;
+    for (uint32_t s = 0; s < kPmDist; s++) nm += sm.fd[s];
+    for (uint32_t s = 257; s < kPtLit; s++) runs += sm.f[s];
+    sm.nmatch = nm;
+    sm.mfix = pm_fixed_bits(sm.fl, sm.fd);
+    sm.pfix = pm_fixed_bits(sm.f, nullptr) + 5ull * runs;  // every run's distance is the 5-bit code 0
+  }
+  __syncthreads();
+  const bool matches = sm.nmatch != 0;  // without one the parse is the parent's
+  if (dynamic) {
+    pt_build(sm.f, sm.po, sm.work, sm.seq, t, 256u, [] { __syncthreads(); });
+    if (matches) pm_build(sm.fl, sm.fd, sm.mo, sm.work, sm.seq, t, 256u, [] { __syncthreads(); });
+  }
+  if (t == 0) {
+    uint32_t which = 0;
+    uint64_t best = sm.pfix;
+    if (dynamic && sm.po.dyn_bits < best) which = 1, best = sm.po.dyn_bits;
+    if (matches && sm.mfix < best) which = 2, best = sm.mfix;
+    if (matches && dynamic && sm.mo.dyn_bits < best) which = 3;
+    sm.which = which;
+  }
+  __syncthreads();
+  const uint32_t which = sm.which;
+  DG_GLOBAL uint32_t *w = gp<uint32_t>(e.words);
+  if (which == 1) {
+    for (uint32_t i = t; i < kPtTableWords; i += 256) tab[i] = sm.po.table[i];
+    for (uint32_t i = t; i < (sm.po.hdr_bits + 31) / 32; i += 256) w[i] = sm.po.hdr[i];
+  } else if (which == 3) {
+    for (uint32_t i = t; i < kPtTableWords; i += 256) tab[kPmLitAt + i] = sm.mo.table[i];
+    if (t < 32) tab[kPmDistAt + t] = sm.mo.dtable[t];
+    for (uint32_t i = t; i < (sm.mo.hdr_bits + 31) / 32; i += 256) w[i] = sm.mo.hdr[i];
+  }
+  if (t == 0 && which) {
+    e.mode = which >= 2;
+    if (which != 2) {
+      e.dyn = 1;
+      e.hdr_bits = which == 1 ? sm.po.hdr_bits : sm.mo.hdr_bits;
+      e.eob_len = (uint16_t)(which == 1 ? sm.po.litlen[256] : sm.mo.litlen[256]);
+    }
+  }
+}
+
+// the image's tables if it took a dynamic block, nullptr for the fixed code
+__device__ __forceinline__ const DG_GLOBAL uint32_t *pm_tabs(const EncDesc &e) {
+  return e.dyn ? gp<const uint32_t>(e.tab) + kPmLitAt : nullptr;
+}
+
+__global__ __launch_bounds__(64) void k_penc_mcount(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  const WgItem it = list[blockIdx.x];
+  const ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  const EncDesc &e = im.enc;
+  if (!e.mode || !e.jopt) return;
+  const uint32_t pc = it.item0, lane = threadIdx.x;
+  const DG_GLOBAL uint32_t *reg = gp<const uint32_t>(e.jopt);
+  uint32_t bits = reg[pc];
+  if (e.dyn) {
+    const DG_GLOBAL uint32_t *tabs = pm_tabs(e), *tok = reg + 2 * (size_t)e.nblocks + (size_t)pc * kPencPiece;
+    const uint32_t n = reg[e.nblocks + pc];
+    bits = 0;
+    for (uint32_t i = lane; i < n; i += 64) pm_token(tok[i], tabs, [&](uint32_t, uint32_t nb) { bits += nb; });
+    bits = wave_sum(bits);
+  }
+  if (lane == 0) gp<uint32_t>(e.bits)[pc] = bits;
+}
+
+__global__ __launch_bounds__(64) void k_penc_mwrite(const ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  const WgItem it = list[blockIdx.x];
+  const ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  const EncDesc &e = im.enc;
+  if (!e.mode || !e.jopt) return;
+  const uint32_t pc = it.item0, lane = threadIdx.x;
+  const DG_GLOBAL uint32_t *reg = gp<const uint32_t>(e.jopt);
+  const DG_GLOBAL uint32_t *tabs = pm_tabs(e), *tok = reg + 2 * (size_t)e.nblocks + (size_t)pc * kPencPiece;
+  const uint32_t n = reg[e.nblocks + pc], per = (n + 63) / 64;
+  const uint32_t lo = min(lane * per, n), hi = min(lo + per, n);
+  uint32_t mine = 0;
+  for (uint32_t i = lo; i < hi; i++) pm_token(tok[i], tabs, [&](uint32_t, uint32_t nb) { mine += nb; });
+  DG_GLOBAL uint32_t *w = gp<uint32_t>(e.words);
+  const uint32_t pos = (e.dyn ? e.hdr_bits : 3u) + gp<const uint32_t>(e.bits)[pc] + wave_scan_excl(mine, lane);
+  uint64_t acc = 0;
+  uint32_t nacc = pos & 31u, wi = pos >> 5;
+  auto emit = [&](uint32_t v, uint32_t nb) {
+    acc |= (uint64_t)v << nacc;
+    nacc += nb;
+    if (nacc >= 32) {
+      atomicOr((uint32_t *)&w[wi], (uint32_t)acc);
+      acc >>= 32;
+      nacc -= 32;
+      wi++;
+    }
+  };
+  for (uint32_t i = lo; i < hi; i++) pm_token(tok[i], tabs, emit);
+  if (lane == 63 && tabs && pc + 1 == e.nblocks) emit(tabs[256] & 0xFFFFu, tabs[256] >> 16);  // the piece's end is lane 63's
+  if (nacc) atomicOr((uint32_t *)&w[wi], (uint32_t)acc);
+  if (pc == 0 && lane == 0 && !tabs) atomicOr((uint32_t *)&w[0], 3u);  // BFINAL = 1, BTYPE = 01
 }
 
 // ------------------------------------------------------------ container
@@ -518,15 +855,35 @@ void launch_penc_count(hipStream_t st, const ImageDesc *imgs, const WgItem *list
 void launch_penc_tree(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   if (nwg) hipLaunchKernelGGL(k_penc_tree, dim3(nwg), dim3(256), 0, st, imgs, list);
 }
-void launch_penc_count_dyn(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
-  if (nwg) hipLaunchKernelGGL(k_penc_count_dyn, dim3(nwg), dim3(256), 0, st, imgs, list);
-}
-void launch_penc_write(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic) {
+void launch_penc_count_dyn(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool match) {
   if (!nwg) return;
-  if (dynamic)
-    hipLaunchKernelGGL(k_penc_write<true>, dim3(nwg), dim3(256), 0, st, imgs, list);
+  if (match)
+    hipLaunchKernelGGL(k_penc_count_dyn<true>, dim3(nwg), dim3(256), 0, st, imgs, list);
   else
-    hipLaunchKernelGGL(k_penc_write<false>, dim3(nwg), dim3(256), 0, st, imgs, list);
+    hipLaunchKernelGGL(k_penc_count_dyn<false>, dim3(nwg), dim3(256), 0, st, imgs, list);
+}
+void launch_penc_write(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic, bool match) {
+  if (!nwg) return;
+  if (match && dynamic)
+    hipLaunchKernelGGL((k_penc_write<true, true>), dim3(nwg), dim3(256), 0, st, imgs, list);
+  else if (match)
+    hipLaunchKernelGGL((k_penc_write<false, true>), dim3(nwg), dim3(256), 0, st, imgs, list);
+  else if (dynamic)
+    hipLaunchKernelGGL((k_penc_write<true, false>), dim3(nwg), dim3(256), 0, st, imgs, list);
+  else
+    hipLaunchKernelGGL((k_penc_write<false, false>), dim3(nwg), dim3(256), 0, st, imgs, list);
+}
+void launch_penc_match(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_penc_match, dim3(nwg), dim3(64), 0, st, imgs, list);
+}
+void launch_penc_mtree(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic) {
+  if (nwg) hipLaunchKernelGGL(k_penc_mtree, dim3(nwg), dim3(256), 0, st, imgs, list, dynamic);
+}
+void launch_penc_mcount(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_penc_mcount, dim3(nwg), dim3(64), 0, st, imgs, list);
+}
+void launch_penc_mwrite(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_penc_mwrite, dim3(nwg), dim3(64), 0, st, imgs, list);
 }
 void launch_penc_final(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   if (nwg) hipLaunchKernelGGL(k_penc_final, dim3(nwg), dim3(1024), 0, st, imgs, list);

@@ -271,4 +271,109 @@ DG_HD void pt_build(const uint32_t *f, PtOut &o, PtWork &k, uint8_t *len_seq, ui
   sync();
 }
 
+// ---- option "penc_match": tokens with distances (DESIGN.md "Matches (option penc_match)")
+
+constexpr uint32_t kPmDist = 30;                   // distance symbols 0..29 (the 8 KiB window reaches 25)
+constexpr uint32_t kPmSeq = kPtLit + kPmDist;      // both alphabets' lengths as one run-length coded sequence
+constexpr uint32_t kPmHdrWords = 144;              // 14 + 19 * 3 + 316 * 14 = 4495 bits at the most
+constexpr uint32_t kPmLitAt = kPtTableWords;       // words of the image's table region: [0, 288) the parent
+constexpr uint32_t kPmDistAt = 2 * kPtTableWords;  // tokens' histogram / table, then the match tokens' two
+constexpr uint32_t kPmTableWords = 2 * kPtTableWords + 32;
+
+struct PmOut {
+  uint32_t table[kPtTableWords];  // as PtOut::table
+  uint32_t dtable[32];            // per distance symbol: bit-reversed code | length << 16
+  uint32_t hdr[kPmHdrWords];
+  uint16_t tok[kPmSeq + 2];
+  uint8_t litlen[kPtTableWords], distlen[32];
+  uint8_t cllen[kPtCl];
+  uint16_t clcode[kPtCl];
+  uint32_t clfreq[kPtCl];
+  uint32_t ntok, hlit, hdist, hclen, hdr_bits;
+  uint64_t dyn_bits;
+};
+
+// distance 1..32768 -> symbol, extra bits and their value (RFC 1951 3.2.5)
+DG_HD void pm_dist_code(uint32_t d, uint32_t &sym, uint32_t &eb, uint32_t &ev) {
+  const uint32_t v = d - 1;
+  if (v < 4) {
+    sym = v;
+    eb = ev = 0;
+    return;
+  }
+  uint32_t hb = 2;  // highest set bit of v
+  while (v >> (hb + 1)) hb++;
+  eb = hb - 1;
+  sym = 2 * hb + ((v >> eb) & 1u);
+  ev = v & ((1u << eb) - 1u);
+}
+DG_HD uint32_t pm_dist_extra(uint32_t sym) { return sym < 4 ? 0u : (sym >> 1) - 1u; }
+
+// A whole fixed block of tokens counted by symbol (fl[256] = 1): header, tokens, end-of-block.
+// fd = nullptr: without the distances' bits.
+DG_HD uint64_t pm_fixed_bits(const uint32_t *fl, const uint32_t *fd) {
+  uint64_t n = 3;
+  for (uint32_t s = 0; s < kPtLit; s++) n += (uint64_t)fl[s] * (pt_fixed_len(s) + (s > 256 ? pt_len_extra(s) : 0u));
+  for (uint32_t s = 0; fd && s < kPmDist; s++) n += (uint64_t)fd[s] * (5u + pm_dist_extra(s));
+  return n;
+}
+
+// The dynamic block of the match tokens, from their two histograms (fl[256] = 1,
+// at least one distance used): code lengths and codes of both alphabets, the
+// header with HDIST = the highest used distance symbol, the block's bits.
+// len_seq: kPmSeq + 4 bytes of scratch.
+template <class Sync>
+DG_HD void pm_build(const uint32_t *fl, const uint32_t *fd, PmOut &o, PtWork &k, uint8_t *len_seq, uint32_t lane,
+                    uint32_t lanes, Sync sync) {
+  pt_lengths(fl, kPtLit, 15, o.litlen, k, lane, lanes, sync);
+  pt_lengths(fd, kPmDist, 15, o.distlen, k, lane, lanes, sync);
+  if (lane == 0) {
+    uint32_t top = 256, dtop = 0, n = 0;
+    for (uint32_t s = 257; s < kPtLit; s++)
+      if (o.litlen[s]) top = s;
+    for (uint32_t s = 0; s < kPmDist; s++)
+      if (o.distlen[s]) dtop = s;
+    o.hlit = top + 1 - 257;
+    o.hdist = dtop;
+    for (uint32_t s = 0; s <= top; s++) len_seq[n++] = o.litlen[s];
+    for (uint32_t s = 0; s <= dtop; s++) len_seq[n++] = o.distlen[s];
+    o.ntok = pt_rle(len_seq, n, o.tok);
+    for (uint32_t s = 0; s < kPtCl; s++) o.clfreq[s] = 0;
+    for (uint32_t t = 0; t < o.ntok; t++) o.clfreq[o.tok[t] & 31u]++;
+  }
+  sync();
+  pt_lengths(o.clfreq, kPtCl, 7, o.cllen, k, lane, lanes, sync);
+  for (uint32_t i = lane; i < kPmHdrWords; i += lanes) o.hdr[i] = 0;
+  sync();
+  if (lane == 0) {
+    pt_codes(o.litlen, kPtLit, [&](uint32_t s, uint32_t r, uint32_t n) { o.table[s] = r | n << 16; });
+    o.table[286] = o.table[287] = 0;
+    pt_codes(o.distlen, kPmDist, [&](uint32_t s, uint32_t r, uint32_t n) { o.dtable[s] = r | n << 16; });
+    o.dtable[30] = o.dtable[31] = 0;
+    pt_codes(o.cllen, kPtCl, [&](uint32_t s, uint32_t r, uint32_t) { o.clcode[s] = (uint16_t)r; });
+    uint32_t last = 0;
+    for (uint32_t i = 0; i < kPtCl; i++)
+      if (o.cllen[pt_cl_order(i)]) last = i;
+    o.hclen = (last + 1 < 4 ? 4 : last + 1) - 4;
+    PtBits b = {o.hdr, 0};
+    pt_put(b, 1, 1);  // BFINAL
+    pt_put(b, 2, 2);  // BTYPE = 10
+    pt_put(b, o.hlit, 5);
+    pt_put(b, o.hdist, 5);
+    pt_put(b, o.hclen, 4);
+    for (uint32_t i = 0; i < o.hclen + 4; i++) pt_put(b, o.cllen[pt_cl_order(i)], 3);
+    for (uint32_t t = 0; t < o.ntok; t++) {
+      const uint32_t s = o.tok[t] & 31u, x = o.tok[t] >> 5;
+      pt_put(b, o.clcode[s], o.cllen[s]);
+      if (s >= 16) pt_put(b, x, s == 16 ? 2 : s == 17 ? 3 : 7);
+    }
+    o.hdr_bits = b.n;
+    uint64_t dyn = b.n;
+    for (uint32_t s = 0; s < kPtLit; s++) dyn += (uint64_t)fl[s] * (o.litlen[s] + (s > 256 ? pt_len_extra(s) : 0u));
+    for (uint32_t s = 0; s < kPmDist; s++) dyn += (uint64_t)fd[s] * (o.distlen[s] + pm_dist_extra(s));
+    o.dyn_bits = dyn;
+  }
+  sync();
+}
+
 }  // namespace dg

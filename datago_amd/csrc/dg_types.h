@@ -436,6 +436,10 @@ struct EncTables {
   uint8_t len[4][256];
 };
 constexpr uint32_t kPencTabBytes = 1280;  // png, option "penc_dynamic": 288 words of histogram / code table, padded to 256
+// png, option "penc_match": 608 words (the parent tokens' histogram / table, the match tokens' two; dg_penc_tree.h),
+// padded to 256; per piece of the stream two counters (bits under the fixed code, tokens) and 1024 token words
+constexpr uint32_t kPencMatchTabBytes = 2560;
+constexpr uint32_t kPencMatchPieceBytes = 8 + 4096;
 struct EncDesc {
   uint64_t src;        // the transformed image (C channels, row stride src_stride)
   uint64_t coef;       // int16 [nblocks][64], quantised, zigzag order, MCU-interleaved blocks
@@ -458,6 +462,8 @@ struct EncDesc {
   // jpeg, option "jenc_optimize" (dg_jenc_tree.h): jopt = the image's histogram / EncTables / DHT region (0: option
   // off).  k_enc_tree sets tab, hdr_len, dht_len and dyn = 1 for an image that takes its own tables, and puts
   // tab_std, hdr_std and dyn = 0 back for one that keeps the standard ones.
+  // png, option "penc_match": jopt = the match parse's region (uint32 bits[nblocks], ntok[nblocks], then 1024 token
+  // words per piece; 0: option off); mode 1 = the image took the match tokens (k_penc_mtree), dyn as above
   uint64_t jopt, tab_std;
   uint32_t hdr_std, dht_len;
   uint16_t hdr_pre, hdr_sos;     // the host's header: bytes in front of its DHT segments; offset of its SOS segment

@@ -242,7 +242,7 @@ const int kNumOptions = (int)(sizeof(kOptionTable) / sizeof(kOptionTable[0]));
 // (tests/test_vp8_cpu.py for "webp_lossy", tests/test_alph_cpu.py for
 // "webp_alpha", tests/test_bmp_cpu.py for "bmp", tests/test_tiff_cpu.py for
 // "tiff", tests/test_tiff_deflate_cpu.py for "tiff_deflate", tests/test_tiff16_cpu.py
-// for "tiff16").  find_option looks through both, so to dg_ctx_set_option the
+// for "tiff16", tests/test_penc_match_cpu.py for "penc_match").  find_option looks through both, so to dg_ctx_set_option the
 // two tables are one.
 const OptRow kOptionTableAdded[] = {
     // Still lossy WebP files (a `VP8 ` image chunk, simple or behind VP8X, no
@@ -323,6 +323,16 @@ const OptRow kOptionTableAdded[] = {
     // encoder; into the JPEG encoder it is DG_ERR_UNSUPPORTED.  16-bit
     // WhiteIsZero is refused: libtiff and the tiff crate disagree on it.
     STRICT("tiff16", tiff16),
+    // PNG re-encode (pre_encode_images, encode_format png): 1 = the filtered
+    // stream is also parsed with LZ77 matches (near distances 1, C, 2C and one
+    // hashed candidate inside an 8 KiB window, k_penc_match in dg_penc.hip),
+    // and an image whose DEFLATE block is strictly shorter with those tokens
+    // takes it -- under the fixed code, or with "penc_dynamic" under codes of
+    // its own for both alphabets (pm_build, dg_penc_tree.h).  Every other
+    // image, and every image with 0 (the default), gets the file it got
+    // before, byte for byte.  Composes with "penc16".  Nothing changes for
+    // JPEG re-encoding.
+    STRICT("penc_match", penc_match),
 };
 const int kNumOptionsAdded = (int)(sizeof(kOptionTableAdded) / sizeof(kOptionTableAdded[0]));
 

@@ -96,6 +96,7 @@ struct Options {
   bool resize16 = false;               // option "resize16": ... and resize to their bucket (dg_resize16.hip)
   bool penc16 = false;                 // option "penc16": ... and go into the PNG re-encoder as 16-bit samples (dg_penc16.h)
   bool penc_dynamic = false;           // option "penc_dynamic": PNG re-encode with per-image Huffman codes where shorter
+  bool penc_match = false;             // option "penc_match": PNG re-encode with LZ77 matches where shorter (k_penc_match)
   bool jenc_optimize = false;          // option "jenc_optimize": JPEG re-encode with per-image Huffman tables
 
   // progressive JPEGs

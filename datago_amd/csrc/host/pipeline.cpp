@@ -1686,14 +1686,21 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     launch_enc_count(sl.st, dd, lst(L_ENC_BLK), cnt(L_ENC_BLK));
     launch_penc_filter(sl.st, dd, lst(L_PENC_ROW), cnt(L_PENC_ROW));
     launch_penc_filter16(sl.st, dd, lst(L_PENC_ROW16), cnt(L_PENC_ROW16));
-    launch_penc_count(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE), b.penc_dyn);
-    if (b.penc_dyn) {  // per-image codes and the block choice, then the chosen images' pieces under their codes
+    launch_penc_count(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE), b.penc_dyn || b.penc_match);
+    if (b.penc_match) {  // the match parse and the choice among up to four blocks; an image that keeps the parent's
+                         // tokens goes on through the parent's kernels, one that takes matches through the token ones
+      launch_penc_match(sl.st, dd, lst(L_PENC_MATCH), cnt(L_PENC_MATCH));
+      launch_penc_mtree(sl.st, dm, lst(L_PENC_IMG), cnt(L_PENC_IMG), b.penc_dyn);
+      if (b.penc_dyn) launch_penc_count_dyn(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE), true);
+      launch_penc_mcount(sl.st, dd, lst(L_PENC_MATCH), cnt(L_PENC_MATCH));
+    } else if (b.penc_dyn) {  // per-image codes and the block choice, then the chosen images' pieces under their codes
       launch_penc_tree(sl.st, dm, lst(L_PENC_IMG), cnt(L_PENC_IMG));
-      launch_penc_count_dyn(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE));
+      launch_penc_count_dyn(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE), false);
     }
     launch_enc_scan(sl.st, dm, lst(L_ENC_IMG), cnt(L_ENC_IMG));
     launch_enc_write(sl.st, dd, lst(L_ENC_BLK), cnt(L_ENC_BLK));
-    launch_penc_write(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE), b.penc_dyn);
+    launch_penc_write(sl.st, dd, lst(L_PENC_PIECE), cnt(L_PENC_PIECE), b.penc_dyn, b.penc_match);
+    if (b.penc_match) launch_penc_mwrite(sl.st, dd, lst(L_PENC_MATCH), cnt(L_PENC_MATCH));
     launch_enc_stuff(sl.st, dm, lst(L_ENC_IMG), cnt(L_ENC_IMG));
     launch_penc_final(sl.st, dm, lst(L_PENC_IMG), cnt(L_PENC_IMG));
   }

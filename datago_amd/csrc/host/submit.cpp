@@ -142,6 +142,7 @@ struct Offs {
   size_t final_off, tmp, out, ds, mk, chunk, stage;
   size_t zs, raw, unf, pal;
   size_t tout, ecoef, ebits, ewords, hdr, eaux;  // JPEG / PNG re-encode
+  size_t emtok = 0;  // PNG, option "penc_match": the match parse's piece counters and tokens (0: option off)
   size_t etab;  // PNG, option "penc_dynamic": bytes of histogram / code table at the head of ewords;
                 // JPEG, option "jenc_optimize": bytes of histogram / EncTables / DHT segments there
   // alpha programs: buffer = dst of pass `stage` (-1: the decoded image), byte offset
@@ -1211,9 +1212,14 @@ void Context::layout_output_and_encode(const SubmitArgs &a, int i, int last_stag
     e.dyn = 0;
     // option "penc_dynamic": the image's histogram / code table (dg_penc_tree.h) in front of its bit buffer,
     // inside the region the batch zeroes
-    o.etab = opt_.penc_dynamic ? kPencTabBytes : 0;
+    // option "penc_match": a larger region (the match tokens' two histograms / tables behind the parent's) and,
+    // in the scratch arena, the piece counters and one token word per stream byte (kPencMatchPieceBytes)
+    o.etab = opt_.penc_match ? kPencMatchTabBytes : opt_.penc_dynamic ? kPencTabBytes : 0;
     o.ewords += o.etab;
+    e.mode = 0;
+    o.emtok = opt_.penc_match ? bl.L.take((size_t)e.nblocks * kPencMatchPieceBytes, 256) : 0;
     b.penc_dyn = b.penc_dyn || opt_.penc_dynamic;
+    b.penc_match = b.penc_match || opt_.penc_match;
     b.any_enc = true;
   } else if (p.encode) {  // the transform lands in tout; the JPEG goes to the caller's buffer
     EncDesc &e = d.enc;
@@ -1468,8 +1474,10 @@ void Context::patch_addresses(const SubmitArgs &a, Slot &sl, Batch &b, const Bat
       e.coef = (uint64_t)(uintptr_t)(S + o.ecoef);
       e.bits = (uint64_t)(uintptr_t)(S + o.ebits);
       e.words = (uint64_t)(uintptr_t)(S + o.ewords + o.etab);
-      if (e.png) e.tab = o.etab ? (uint64_t)(uintptr_t)(S + o.ewords) : 0;
-      else e.jopt = o.etab ? (uint64_t)(uintptr_t)(S + o.ewords) : 0;
+      if (e.png) {
+        e.tab = o.etab ? (uint64_t)(uintptr_t)(S + o.ewords) : 0;
+        e.jopt = o.emtok ? (uint64_t)(uintptr_t)(S + o.emtok) : 0;
+      } else e.jopt = o.etab ? (uint64_t)(uintptr_t)(S + o.ewords) : 0;
       e.aux = o.eaux ? (uint64_t)(uintptr_t)(S + o.eaux) : 0;
       e.hdr = o.hdr + 1;  // blob offset + 1: made absolute with the meta buffer
     }
@@ -1851,6 +1859,8 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
     for (uint32_t it = 0; it < e.nblocks; it += 256) b.lists[L_PENC_PIECE].push_back({I, it});
     b.lists[L_ENC_IMG].push_back({I, 0});  // k_enc_scan: piece offsets
     b.lists[L_PENC_IMG].push_back({I, 0});
+    if (opt_.penc_match)
+      for (uint32_t it = 0; it < e.nblocks; it++) b.lists[L_PENC_MATCH].push_back({I, it});
   } else if (d.enc.active) {
     const EncDesc &e = d.enc;
     for (uint32_t it = 0; it < e.nbx * e.nby; it += 256) b.lists[L_ENC_MCU].push_back({I, it});

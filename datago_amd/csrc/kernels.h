@@ -182,7 +182,15 @@ void launch_penc_filter16(hipStream_t st, const ImageDesc *imgs, const WgItem *l
 // codes and chooses the block; count_dyn re-counts the pieces of the images that took the dynamic block
 void launch_penc_count(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic);
 void launch_penc_tree(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
-void launch_penc_count_dyn(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
-void launch_penc_write(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic);
+// match (option "penc_match"): count_dyn and write leave the images that took the match tokens (EncDesc::mode) alone
+void launch_penc_count_dyn(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool match);
+void launch_penc_write(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic, bool match);
+// option "penc_match", one piece per workgroup of one wave: the match parse into the token buffer; the images'
+// choice among the parent's blocks and the match tokens' (1 image per workgroup; dynamic: option "penc_dynamic");
+// the pieces' bits and their codes for the images that took the match tokens
+void launch_penc_match(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_penc_mtree(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg, bool dynamic);
+void launch_penc_mcount(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
+void launch_penc_mwrite(hipStream_t st, const ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_penc_final(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 }  // namespace dg

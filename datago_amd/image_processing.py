@@ -90,7 +90,7 @@ class ARAwareTransform:
     def __init__(self, cfg: ImageTransformConfig, device: int = 0, png16: bool = False, resize16: bool = False,
                  penc_dynamic: bool = False, penc16: bool = False, jenc_optimize: bool = False, gif: bool = False,
                  webp: bool = False, webp_lossy: bool = False, webp_alpha: bool = False, bmp: bool = False,
-                 tiff: bool = False, tiff16: bool = False):
+                 tiff: bool = False, tiff16: bool = False, penc_match: bool = False):
         self.cfg = cfg
         self.tiff16 = tiff16  # context option "tiff16": with tiff, a TIFF of 16-bit samples decodes on the GPU as uint16
         self.tiff = tiff  # context option "tiff": an 8-bit chunky TIFF decodes on the GPU as L8 / LA8 / RGB8 / RGBA8
@@ -101,6 +101,7 @@ class ARAwareTransform:
         self.gif = gif  # context option "gif": a GIF's first frame decodes on the GPU as RGBA8
         self.jenc_optimize = jenc_optimize  # context option "jenc_optimize": JPEG re-encode with per-image Huffman tables
         self.penc_dynamic = penc_dynamic  # context option "penc_dynamic": PNG re-encode with per-image Huffman codes
+        self.penc_match = penc_match  # context option "penc_match": PNG re-encode with LZ77 matches
         self.png16 = png16  # context option "png16": 16-bit PNGs of a bucket's size decode on the GPU
         self.resize16 = resize16  # context option "resize16": ... and every other 16-bit PNG resizes to its bucket
         self.penc16 = penc16  # context option "penc16": ... and pre-encodes as a bit-depth-16 PNG (encode_format png)
@@ -128,7 +129,8 @@ class ARAwareTransform:
                                           image_to_rgb8=enc.img_to_rgb8, pre_encode_images=enc.encode_images,
                                           encode_format=int(enc.encode_format), jpeg_quality=enc.jpeg_quality,
                                           png16=self.png16, resize16=self.resize16, penc16=self.penc16,
-                                          penc_dynamic=self.penc_dynamic, jenc_optimize=self.jenc_optimize,
+                                          penc_dynamic=self.penc_dynamic, penc_match=self.penc_match,
+                                          jenc_optimize=self.jenc_optimize,
                                           gif=self.gif, webp=self.webp, webp_lossy=self.webp_lossy,
                                           webp_alpha=self.webp_alpha, bmp=self.bmp, tiff=self.tiff,
                                           tiff16=self.tiff16)

@@ -489,6 +489,12 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 dynamic block (RFC 1951 3.2.7; DESIGN.md "PNG re-encode" states the bytes); every other
  *                 image keeps the fixed block.  Default 0: the fixed block always, byte for byte as
  *                 before.  The bound dg_output_size reports is the same; JPEG re-encoding ignores it
+ *   "penc_match"  1 = PNG re-encode: the filtered stream is also parsed with LZ77 matches (distances 1, C, 2C
+ *                 and one hashed candidate within 8 KiB; DESIGN.md "Matches (option penc_match)" states the
+ *                 parse), and an image whose DEFLATE block is strictly shorter with them takes that block,
+ *                 under the fixed code or, with "penc_dynamic", under codes of its own for both alphabets.
+ *                 Every other image gets the file it had.  Default 0: nothing changes.  Composes with
+ *                 "penc16"; the bound dg_output_size reports is the same; JPEG re-encoding ignores it
  *   "jenc_optimize" 1 = JPEG re-encode (pre_encode_images with encode_format jpeg): every image is coded
  *                 with Huffman tables built from its own symbol counts by libjpeg's jpeg_gen_optimal_table
  *                 rule (T.81 K.2 + K.3, what optimize_coding gives; DESIGN.md "JPEG re-encode" states it)

@@ -8,7 +8,7 @@ of 5 timed submissions after 3 warm-up ones, one batch in flight: a latency
 figure, not the pipelined rate of bench.py.  Per context: ms per batch and the
 total encoded bytes (and their ratio to the raw pixels).
 
-    python tools/penc_bench.py [--n 24] [--steps 5] [--warmup 3] [--only both|fixed|dynamic] [--out result.json]
+    python tools/penc_bench.py [--n 24] [--steps 5] [--warmup 3] [--only both|all|fixed|dynamic|match] [--patterned] [--out result.json]
 
 Under rocprofv3 --kernel-trace --stats the same run gives the times of
 k_penc_tree and of the count / write kernels (pass --only dynamic to leave the
@@ -31,11 +31,31 @@ def make_files(n: int, w: int, h: int):
     return [synth.make_jpeg(700 + i, w, h, 92, "4:2:0") for i in range(n)]
 
 
+def make_patterned(n: int, size: int = 512):
+    """Masks and tiles, the images "penc_match" is for: checkers, a dithered ramp and tiled noise as PNG files."""
+    y, x = np.mgrid[0:size, 0:size]
+    bayer = np.array([[0, 8, 2, 10], [12, 4, 14, 6], [3, 11, 1, 9], [15, 7, 13, 5]])
+    out = []
+    for i in range(n):
+        rng = np.random.default_rng(900 + i)
+        kind = i % 4
+        if kind == 0:
+            px = np.repeat(((((x >> (i // 4 % 3)) + y) & 1) * 255)[:, :, None], 3, axis=2)
+        elif kind == 1:
+            px = np.repeat((x // 2 + bayer[y & 3, x & 3] * 16 >= 256)[:, :, None] * 255, 3, axis=2)
+        else:
+            t = 8 << (kind - 2)
+            px = np.tile(rng.integers(0, 256, (t, t, 3)), (size // t, size // t, 1))
+        px = np.ascontiguousarray(px, np.uint8)
+        out.append(synth.encode_png(px.reshape(size, size * 3), size, size, 8, 2, 3, rng, level=1, filters="none"))
+    return out
+
+
 def run(ctx, files, steps: int, warmup: int):
     blob = np.concatenate([np.frombuffer(f, np.uint8) for f in files])
     offs = np.cumsum([0] + [len(f) for f in files])[:-1]
-    host = np.ascontiguousarray(blob)
-    ctx.host_register(host)
+    host = ctx.host_alloc(blob.nbytes)  # page-locked from the start: existing memory cannot always be registered
+    host[:] = blob
     d_in = ctx.alloc(host.nbytes + 64)
     ctx.h2d(d_in, host)
     sizes = []
@@ -59,7 +79,7 @@ def run(ctx, files, steps: int, warmup: int):
     enc = sum(int(metas[i].nbytes) for i in range(len(files)))
     raw = sum(int(metas[i].width) * int(metas[i].height) * 3 for i in range(len(files)))
     med = statistics.median(ms)
-    ctx.host_unregister(host)
+    ctx.host_free(host)
     return {"ms_per_batch": round(med, 3), "runs_ms": [round(v, 3) for v in ms], "encoded_bytes": enc,
             "raw_pixel_bytes": raw, "encoded_over_raw": round(enc / raw, 4)}
 
@@ -69,10 +89,11 @@ def main() -> int:
     ap.add_argument("--n", type=int, default=24)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--only", choices=["both", "fixed", "dynamic"], default="both")
+    ap.add_argument("--only", choices=["both", "all", "fixed", "dynamic", "match"], default="both")
+    ap.add_argument("--patterned", action="store_true", help="a batch of 512 x 512 masks and tiles at their own size")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    files = make_files(a.n, 1024, 768)
+    files = make_patterned(a.n) if a.patterned else make_files(a.n, 1024, 768)
     kw = dict(crop_and_resize=True, default_image_size=512, downsampling_ratio=32, min_aspect_ratio=0.5,
               max_aspect_ratio=2.0, pre_encode_images=True, encode_format=0)
     res = {}
@@ -80,6 +101,11 @@ def main() -> int:
         res["fixed"] = run(L.Context(0, **kw), files, a.steps, a.warmup)
     if a.only in ("both", "dynamic"):
         res["dynamic"] = run(L.Context(0, penc_dynamic=True, **kw), files, a.steps, a.warmup)
+    if a.only in ("all", "match"):  # "penc_match" beside "penc_dynamic": the choice among all four blocks
+        if a.only == "all":
+            res["fixed"] = run(L.Context(0, **kw), files, a.steps, a.warmup)
+            res["dynamic"] = run(L.Context(0, penc_dynamic=True, **kw), files, a.steps, a.warmup)
+        res["match"] = run(L.Context(0, penc_dynamic=True, penc_match=True, **kw), files, a.steps, a.warmup)
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
