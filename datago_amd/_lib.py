@@ -335,7 +335,7 @@ class Context:
                  resize16: bool = False, penc_dynamic: bool = False, penc16: bool = False,
                  jenc_optimize: bool = False, gif: bool = False, webp: bool = False, webp_lossy: bool = False,
                  webp_alpha: bool = False, bmp: bool = False, tiff: bool = False, tiff_deflate: bool = False,
-                 tiff16: bool = False, penc_match: bool = False):
+                 tiff16: bool = False, penc_match: bool = False, tiff_bilevel: bool = False):
         L = load()
         cfg = ImageConfig(int(crop_and_resize), default_image_size, downsampling_ratio, min_aspect_ratio,
                           max_aspect_ratio, int(pre_encode_images), int(image_to_rgb8), encode_format,
@@ -373,7 +373,9 @@ class Context:
                 # with tiff, Deflate-compressed TIFFs (compression 8 / 32946) too; off: DG_ERR_UNSUPPORTED
                 ("tiff_deflate", tiff_deflate),
                 # with tiff, TIFFs of 16-bit samples too: L16 / La16 / Rgb16 / Rgba16 as uint16; off: DG_ERR_UNSUPPORTED
-                ("tiff16", tiff16)):
+                ("tiff16", tiff16),
+                # with tiff, 1-bit TIFFs too (raw, PackBits, LZW, Deflate, CCITT Group 4): L8 of 0 / 255; off: DG_ERR_UNSUPPORTED
+                ("tiff_bilevel", tiff_bilevel)):
             if on:
                 self.set_option(key, 1)
 

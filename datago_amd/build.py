@@ -32,6 +32,7 @@ SOURCES = [
     ("dg_bmp.hip", True),
     ("dg_tiff.hip", True),
     ("dg_tiff_inflate.hip", True),
+    ("dg_tiff_g4.hip", True),
     ("dg_vp8l.hip", True),
     ("dg_vp8.hip", True),
     ("dg_alph.hip", True),

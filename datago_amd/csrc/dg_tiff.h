@@ -16,7 +16,8 @@
 // Expand.  A lane holds four pixels as four dwords, sample s of a pixel in byte s
 // (tiff_px); predictor 2 is a prefix sum per byte lane, modulo 256 (tiff_badd), and
 // tiff_pack turns the four pixels back into the 4 x spp bytes of the row.  The 16-bit form
-// (k_tiff_expand16; tests/native/tiff16_emu.cpp on the CPU) is the tiff16_* routines below.
+// (k_tiff_expand16; tests/native/tiff16_emu.cpp on the CPU) is the tiff16_* routines below, the
+// 1-bit form (k_tiff_expand1; tests/native/tiff_g4_emu.cpp) is tiff1_spread.
 #pragma once
 #include "dg_gif.h"
 #include "dg_types.h"
@@ -100,6 +101,10 @@ DG_HD uint32_t tiff16_pack(const uint32_t p[4][2], uint32_t m, uint32_t spp) {
   const uint32_t j0 = 2u * m, j1 = j0 + 1u;
   return tiff16_at(p[j0 / spp], j0 % spp) | (tiff16_at(p[j1 / spp], j1 % spp) << 16);
 }
+// ---- expand, 1-bit samples (k_tiff_expand1, option "tiff_bilevel")
+// Four pixels, the first in bit 3 of n, as four bytes of 0 / 255 in memory order: one multiply puts bit 3 - k
+// into byte k, one more turns the 1s into 255s.
+DG_HD uint32_t tiff1_spread(uint32_t n) { return ((((n & 15u) * 0x08040201u) & 0x08080808u) >> 3) * 0xFFu; }
 
 // Row piece pc of an image (a piece is one row of one segment column, pieces run row by row): its image
 // row, its segment, the byte offset of its first pixel inside the segment, its first pixel in the row and

@@ -6,6 +6,8 @@
 //                    predictor 2, WhiteIsZero, strip and tile placement, the edge crop
 //   k_tiff_expand16  the same for 16-bit samples (option "tiff16"): the file's byte order undone,
 //                    predictor 2 on whole samples, native-endian uint16 in the pixel plane
+//   k_tiff_expand1   the same for 1-bit samples (option "tiff_bilevel"): packed rows, MSB first, to
+//                    L8 of 0 / 255
 //
 // What they restate: the tiff crate as image 0.25's TiffDecoder drives it for
 // load_from_memory, for the files it and libtiff (Pillow) decode to the same bytes;
@@ -47,6 +49,12 @@
 // samples are swapped two at a time by one byte permute; predictor 2 regroups a pixel's samples
 // into ceil(spp / 2) dwords so that the sums are packed 16-bit adds (v_pk_add_u16), scanned over
 // the wave as above; the stores are 16 bytes wide for spp 2 and 4, 8 bytes for spp 1 and 3.
+//
+// k_tiff_expand1 keeps the split too.  A lane takes 32 pixels: one dword of the packed row, funnel-shifted
+// from two aligned loads at any byte phase, eight nibbles spread to 0 / 255 by two multiplies each
+// (tiff1_spread), WhiteIsZero as an exclusive or, two 16-byte stores.  The bits come from the file in
+// place (compression 1) or from the arena, where k_tiff_g4 (dg_tiff_g4.hip) and the byte decoders leave
+// the same rows.
 //
 // Every loop is bounded by the segment's bit or byte count and its decoded size: a
 // step consumes input or ends the decode.
@@ -534,6 +542,48 @@ __global__ __launch_bounds__(64) void k_tiff_expand16(ImageDesc *__restrict__ im
   }
 }
 
+// ------------------------------------------------------------ expand, 1-bit samples
+
+__global__ __launch_bounds__(64) void k_tiff_expand1(ImageDesc *__restrict__ imgs, const WgItem *__restrict__ list) {
+  const WgItem it = list[blockIdx.x];
+  ImageDesc &im = imgs[it.image];
+  if (im.status) return;
+  const TiffDesc &g = im.tiff;
+  const uint32_t lane = threadIdx.x, W = im.width, rowb = (g.seg_w + 7u) >> 3;
+  const uint32_t pieces = im.height * g.across;
+  const uint32_t inv = g.invert ? ~0u : 0u;  // sample 1 is 255 under BlackIsZero, 0 under WhiteIsZero
+  for (uint32_t pc = it.item0; pc < it.item0 + kTiffExpandPieces && pc < pieces; pc++) {
+    const TiffPiece pp = tiff_piece(pc, W, 1u, g.seg_w, g.seg_h, g.across);
+    const TiffSeg sg = tiff_seg(g.segs, pp.seg);
+    const uint64_t base = g.comp == 1u ? g.file + sg.off : g.dec + sg.dst;
+    const uint64_t end = base + (g.comp == 1u ? sg.nbytes : sg.dec);
+    const uint64_t row = base + (uint64_t)(pp.y % g.seg_h) * rowb;  // (tiff_piece's offset counts a byte per pixel)
+    DG_GLOBAL uint8_t *dst = gp<uint8_t>(im.pix) + (size_t)pp.y * im.pix_stride + pp.px0;
+    for (uint32_t x0 = 32u * lane; x0 < pp.npx; x0 += 2048u) {
+      const uint32_t n = pp.npx - x0 < 32u ? pp.npx - x0 : 32u;
+      const uint64_t A = row + (x0 >> 3), last = A + ((n + 7u) >> 3), A0 = A & ~3ull;
+      const uint32_t r0 = tiff_ld32(A0, end), r1 = A0 + 4u < last ? tiff_ld32(A0 + 4u, end) : 0u;
+      const uint32_t v = __funnelshift_r(r0, r1, (uint32_t)(A & 3ull) * 8u);
+      uint32_t o[8];
+#pragma unroll
+      for (uint32_t t = 0; t < 4; t++) {
+        const uint32_t b = (v >> (8u * t)) & 255u;
+        o[2u * t] = tiff1_spread(b >> 4) ^ inv;
+        o[2u * t + 1u] = tiff1_spread(b) ^ inv;
+      }
+      DG_GLOBAL uint8_t *d = dst + x0;  // on a 32-byte boundary: x0 and the segment column's first pixel are multiples of 16 and 32
+      if (n == 32u) {
+        *(DG_GLOBAL u32x4 *)d = u32x4{o[0], o[1], o[2], o[3]};
+        *(DG_GLOBAL u32x4 *)(d + 16) = u32x4{o[4], o[5], o[6], o[7]};
+      } else {  // the row's ragged end
+#pragma unroll
+        for (uint32_t j = 0; j < 31; j++)
+          if (j < n) d[j] = (uint8_t)(o[j >> 2] >> (8u * (j & 3u)));
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------ launchers
 
 void launch_tiff_lzw(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
@@ -547,6 +597,9 @@ void launch_tiff_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uin
 }
 void launch_tiff_expand16(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
   if (nwg) hipLaunchKernelGGL(k_tiff_expand16, dim3(nwg), dim3(64), 0, st, imgs, list);
+}
+void launch_tiff_expand1(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg) {
+  if (nwg) hipLaunchKernelGGL(k_tiff_expand1, dim3(nwg), dim3(64), 0, st, imgs, list);
 }
 
 }  // namespace dg

@@ -258,7 +258,9 @@ constexpr uint32_t kBmpFailPalette = 4;  // an index at or past the colour table
 // inverts WhiteIsZero and places rows and tiles in the pixel plane (dg_tiff.h, dg_tiff.hip).  A
 // segment that does not decode sets ImageDesc::status and TiffDesc::fail names it.  With option "tiff16"
 // a file of 16-bit samples goes through k_tiff_expand16 instead and leaves L16 / La16 / Rgb16 / Rgba16 as
-// native-endian uint16 (ImageDesc::sample_bytes 2: the plane k_png_expand16 leaves).
+// native-endian uint16 (ImageDesc::sample_bytes 2: the plane k_png_expand16 leaves).  With option
+// "tiff_bilevel" a 1-bit file's segments hold rows of ceil(seg_w / 8) bytes, MSB first: k_tiff_g4
+// (dg_tiff_g4.hip) writes those for a CCITT Group 4 segment, and k_tiff_expand1 turns them into L8 of 0 / 255.
 struct TiffSeg {
   uint32_t off;     // the coded bytes: offset in the file (any byte alignment) ...
   uint32_t nbytes;  // ... and count
@@ -268,17 +270,19 @@ struct TiffSeg {
 struct TiffDesc {
   uint64_t file;      // the file's first byte
   uint64_t segs;      // TiffSeg[nseg] (device)
-  uint64_t dec;       // the decoded arena (compression 5 / 8 / 32773)
+  uint64_t dec;       // the decoded arena (compression 4 / 5 / 8 / 32773)
   uint32_t nseg;
-  uint32_t comp;      // 1, 5 (LZW), 32773 (PackBits) or 8 (Deflate, option "tiff_deflate": k_tiff_inflate, dg_tiff_inflate.hip)
+  uint32_t comp;      // 1, 5 (LZW), 32773 (PackBits), 8 (Deflate, option "tiff_deflate": k_tiff_inflate, dg_tiff_inflate.hip)
+                      // or 4 (Group 4, option "tiff_bilevel": k_tiff_g4, dg_tiff_g4.hip)
   uint32_t pred;      // 1 or 2
   uint32_t invert;    // WhiteIsZero
   uint32_t spp;       // samples per pixel, 1 .. 4
   uint32_t seg_w;     // pixels per segment row: the tile width, or the image width for strips
   uint32_t seg_h;     // rows per segment: the tile length or RowsPerStrip
   uint32_t across;    // segments side by side: tiles per row, 1 for strips
-  uint32_t fail;      // kTiffFail*: written by k_tiff_lzw / k_tiff_packbits / k_tiff_inflate
-  uint32_t bits;      // bits per sample: 8, or 16 (option "tiff16": k_tiff_expand16 instead of k_tiff_expand)
+  uint32_t fail;      // kTiffFail*: written by k_tiff_lzw / k_tiff_packbits / k_tiff_inflate / k_tiff_g4
+  uint32_t bits;      // bits per sample: 8, 16 (option "tiff16": k_tiff_expand16 instead of k_tiff_expand) or
+                      // 1 (option "tiff_bilevel": k_tiff_expand1)
   uint32_t swap;      // 16-bit samples of an MM file: their bytes are exchanged on the way to the pixel plane
 };
 constexpr uint32_t kTiffFailCode = 1;   // an LZW code above the next free one
@@ -286,6 +290,8 @@ constexpr uint32_t kTiffFailShort = 2;  // a segment ends (or its end code comes
 constexpr uint32_t kTiffFailFull = 3;   // an LZW table that stays full for over kTiffFullCodes codes (libtiff refuses it)
 constexpr uint32_t kTiffFailStream = 4; // a zlib header, block header, code set, code or distance that zlib refuses
 constexpr uint32_t kTiffFailSum = 5;    // the Adler-32 after the last block differs from the decoded bytes'
+constexpr uint32_t kTiffFailG4 = 6;     // a Group 4 stream libtiff pads and the fax crate fails: an invalid or extension code, a run
+                                        // past the row's end, a mode without its b1, data that ends before the rows do
 
 // ---- lossless WebP (ImageDesc::fmt == kFmtWebp, option "webp"): a VP8L chunk as Rgb8 / Rgba8.
 // k_vp8l_decode (one wave per image, dg_vp8l.h) reads the bitstream after the 5-byte header in place:

@@ -242,8 +242,9 @@ const int kNumOptions = (int)(sizeof(kOptionTable) / sizeof(kOptionTable[0]));
 // (tests/test_vp8_cpu.py for "webp_lossy", tests/test_alph_cpu.py for
 // "webp_alpha", tests/test_bmp_cpu.py for "bmp", tests/test_tiff_cpu.py for
 // "tiff", tests/test_tiff_deflate_cpu.py for "tiff_deflate", tests/test_tiff16_cpu.py
-// for "tiff16", tests/test_penc_match_cpu.py for "penc_match").  find_option looks through both, so to dg_ctx_set_option the
-// two tables are one.
+// for "tiff16", tests/test_penc_match_cpu.py for "penc_match",
+// tests/test_tiff_bilevel_cpu.py for "tiff_bilevel").  find_option looks through
+// both, so to dg_ctx_set_option the two tables are one.
 const OptRow kOptionTableAdded[] = {
     // Still lossy WebP files (a `VP8 ` image chunk, simple or behind VP8X, no
     // ALPH chunk) on the GPU (default off: nothing changes, see "webp").  1,
@@ -333,6 +334,19 @@ const OptRow kOptionTableAdded[] = {
     // before, byte for byte.  Composes with "penc16".  Nothing changes for
     // JPEG re-encoding.
     STRICT("penc_match", penc_match),
+    // With "tiff" (alone it changes nothing): a TIFF of 1-bit samples
+    // (BitsPerSample 1 or absent, one sample per pixel, either gray
+    // photometric, FillOrder 1) decodes to L8 of 0 / 255 with bit_depth 8
+    // (default off: it stays DG_ERR_UNSUPPORTED "TIFF: samples not 8 bits").
+    // Compression 1, 32773, 5, 8 / 32946 beside "tiff_deflate", and 4: CCITT
+    // Group 4, which k_tiff_g4 (dg_tiff_g4.hip) decodes one segment per wave
+    // into the packed rows a raw segment holds; k_tiff_expand1 (dg_tiff.hip)
+    // spreads those to bytes, so from there the image is an 8-bit gray PNG's
+    // pixels.  Refused with texts of their own: Modified Huffman and Group 3,
+    // Group 4's uncompressed mode, predictor 2, 2- and 4-bit samples, an extra
+    // sample, a Group 4 row wider than 16,384 pixels, and a Group 4 stream
+    // libtiff would pad ("TIFF: irregular Group 4 stream").
+    STRICT("tiff_bilevel", tiff_bilevel),
 };
 const int kNumOptionsAdded = (int)(sizeof(kOptionTableAdded) / sizeof(kOptionTableAdded[0]));
 

@@ -86,6 +86,7 @@ struct Options {
   bool bmp = false;                    // option "bmp": a Windows bitmap decodes on the GPU (dg_bmp.hip)
   bool tiff = false;                   // option "tiff": an 8-bit chunky TIFF decodes on the GPU (dg_tiff.hip)
   bool tiff_deflate = false;           // option "tiff_deflate": with "tiff", Deflate-compressed TIFFs too (dg_tiff_inflate.hip)
+  bool tiff_bilevel = false;           // option "tiff_bilevel": with "tiff", 1-bit TIFFs too, CCITT Group 4 included (dg_tiff_g4.hip, k_tiff_expand1)
   bool tiff16 = false;                 // option "tiff16": with "tiff", TIFFs of 16-bit samples too (k_tiff_expand16, dg_tiff.hip)
   bool webp = false;                   // option "webp": a lossless WebP decodes on the GPU (dg_vp8l.hip)
   bool webp_lossy = false;             // option "webp_lossy": a lossy WebP without alpha decodes on the GPU (dg_vp8.hip)

@@ -1122,15 +1122,15 @@ dg_status Context::plan_image(const uint8_t *h, size_t len, int32_t forced, Imag
     C = (uint32_t)p.bmp.out_c;
   } else if (opt_.tiff && is_tiff(h, len)) {  // option "tiff"
     p.fmt = kFmtTiff;
-    // option "tiff_deflate" admits compression 8 / 32946, option "tiff16" 16-bit samples
-    parse_tiff_header(h, len, p.tiff, opt_.tiff_deflate, opt_.tiff16);
+    // option "tiff_deflate" admits compression 8 / 32946, option "tiff16" 16-bit samples, option "tiff_bilevel" 1-bit ones
+    parse_tiff_header(h, len, p.tiff, opt_.tiff_deflate, opt_.tiff16, opt_.tiff_bilevel);
     if (p.tiff.status != TH_OK) {
       p.status = p.tiff.status == TH_UNSUPPORTED ? DG_ERR_UNSUPPORTED : DG_ERR_CORRUPT;
       return DG_OK;
     }
     // the limits of the BMP path: the pixel buffer and the file stay 32-bit addressable (the decoded arena
     // is held under 2^31 by the header walk)
-    if ((uint64_t)p.tiff.width * p.tiff.height * 4ull * (p.tiff.bits / 8) >= (1ull << 31) || len >= (1ull << 28)) {
+    if ((uint64_t)p.tiff.width * p.tiff.height * 4ull * (p.tiff.bits == 16 ? 2 : 1) >= (1ull << 31) || len >= (1ull << 28)) {
       p.tiff.status = TH_UNSUPPORTED;
       p.tiff.why = "TIFF: image too large for the GPU path";
       p.status = DG_ERR_UNSUPPORTED;
@@ -1532,6 +1532,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
     launch_tiff_lzw(sl.st, dm, lst(L_TIFF_LZW), cnt(L_TIFF_LZW));
     launch_tiff_packbits(sl.st, dm, lst(L_TIFF_PACKBITS), cnt(L_TIFF_PACKBITS));
     launch_tiff_inflate(sl.st, dm, lst(L_TIFF_INFLATE), cnt(L_TIFF_INFLATE));  // (option "tiff_deflate")
+    launch_tiff_g4(sl.st, dm, lst(L_TIFF_G4), cnt(L_TIFF_G4));                 // (option "tiff_bilevel")
   }
   if (!from_fix && b.any_webp) {  // lossless WebP: bitstream -> ARGB plane -> inverse transforms
     launch_vp8l_decode(sl.st, dm, lst(L_VP8L), cnt(L_VP8L));
@@ -1550,6 +1551,7 @@ dg_status Context::launch_all(Slot &sl, bool from_fix) {
   if (!from_fix && b.any_tiff) {
     launch_tiff_expand(sl.st, dm, lst(L_TIFF_EXPAND), cnt(L_TIFF_EXPAND));
     launch_tiff_expand16(sl.st, dm, lst(L_TIFF_EXPAND16), cnt(L_TIFF_EXPAND16));  // (option "tiff16")
+    launch_tiff_expand1(sl.st, dm, lst(L_TIFF_EXPAND1), cnt(L_TIFF_EXPAND1));     // (option "tiff_bilevel")
   }
   if (!from_fix && b.any_webp) launch_vp8l_store(sl.st, dm, lst(L_VP8L_STORE), cnt(L_VP8L_STORE));
   if (!from_fix && b.any_vp8) launch_vp8_rgb(sl.st, dm, lst(L_VP8_RGB), cnt(L_VP8_RGB));
@@ -1934,13 +1936,14 @@ dg_status Context::finish_body(Slot &sl) {
                 : f == kBmpFailPalette ? "BMP: pixel index past the colour table"
                                        : "BMP: decode failed");
     }
-    if (status && back[b.desc_of[i]].fmt == kFmtTiff) {  // what k_tiff_lzw / k_tiff_packbits / k_tiff_inflate met in a segment
+    if (status && back[b.desc_of[i]].fmt == kFmtTiff) {  // what k_tiff_lzw / k_tiff_packbits / k_tiff_inflate / k_tiff_g4 met in a segment
       const uint32_t f = back[b.desc_of[i]].tiff.fail;
       set_error(f == kTiffFailCode    ? "TIFF: LZW code above the next free code"
                 : f == kTiffFailShort ? "TIFF: a segment's data ends before its last row is complete"
                 : f == kTiffFailFull  ? "TIFF: LZW table stays full without a clear code"
                 : f == kTiffFailStream ? "TIFF: malformed Deflate stream (zlib header, block header, code set, code or distance)"
                 : f == kTiffFailSum   ? "TIFF: Adler-32 of a Deflate segment does not match its bytes"
+                : f == kTiffFailG4    ? "TIFF: irregular Group 4 stream"
                                       : "TIFF: decode failed");
     }
     if (status && back[b.desc_of[i]].fmt == kFmtWebp) {  // what k_vp8l_decode met in the stream

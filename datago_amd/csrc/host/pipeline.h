@@ -104,7 +104,7 @@ struct Batch {
   bool any_webp = false;  // a lossless WebP (option "webp") or a VP8L-coded alpha stream: k_vp8l_decode, k_vp8l_inverse, k_vp8l_store
   bool any_alph = false;  // a lossy WebP with an ALPH chunk (option "webp_alpha"): k_alph_plane
   bool any_bmp = false;   // a BMP (option "bmp"): k_bmp_rle, k_bmp_expand
-  bool any_tiff = false;  // a TIFF (option "tiff"): k_tiff_lzw, k_tiff_packbits, k_tiff_inflate, k_tiff_expand
+  bool any_tiff = false;  // a TIFF (option "tiff"): k_tiff_lzw, k_tiff_packbits, k_tiff_inflate, k_tiff_g4, k_tiff_expand
   bool any_vp8 = false;   // a lossy WebP (option "webp_lossy"): k_vp8_parse, k_vp8_recon, k_vp8_filter, k_vp8_rgb
   bool penc_match = false;  // a PNG re-encode with option "penc_match": k_penc_match, k_penc_mtree, token count / write
   bool penc_dyn = false;  // a PNG re-encode with option "penc_dynamic": histogram, k_penc_tree, dynamic count / write
@@ -228,6 +228,7 @@ enum ListId {
   L_TIFF_LZW, L_TIFF_PACKBITS, L_TIFF_EXPAND,               // TIFF decode (dg_tiff.hip): per LZW / PackBits segment, per 4 row pieces
   L_TIFF_INFLATE,                                           // TIFF Deflate (dg_tiff_inflate.hip): per Deflate segment
   L_TIFF_EXPAND16,                                          // 16-bit TIFF (k_tiff_expand16): per 4 row pieces
+  L_TIFF_G4, L_TIFF_EXPAND1,                                // bilevel TIFF (dg_tiff_g4.hip, k_tiff_expand1): per Group 4 segment, per 4 row pieces
   L_PENC_MATCH,                                             // PNG re-encode, option "penc_match": per 1 KiB piece (k_penc_match)
   L_COUNT
 };

@@ -718,6 +718,7 @@ void Context::layout_bmp(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, 
 // segment's bytes, each slot a multiple of 16), the segment table in the blob and the L8 / La8 / Rgb8 / Rgba8
 // pixels, which then are what an 8-bit PNG's pixels are.  16-bit samples (option "tiff16"): two bytes per sample in
 // the arena and in the pixel plane, whose rows of native-endian uint16 are what k_png_expand16 leaves of a 16-bit PNG.
+// 1-bit samples (option "tiff_bilevel"): eight pixels to a byte in the arena, L8 of 0 / 255 in the pixel plane.
 void Context::layout_tiff(const SubmitArgs &a, int i, Batch &b, BatchLayout &bl, ImageDesc &d, Offs &o) {
   const TiffHeader &g = b.plans[i].tiff;
   d.fmt = kFmtTiff;
@@ -1752,9 +1753,9 @@ void Context::image_items(int di, Batch &b, ClassLists &cl) {
     b.lists[L_VP8L].push_back({I, 0});
     for (uint32_t it = 0; it < d.width * d.height; it += 256) b.lists[L_VP8L_STORE].push_back({I, it});
   } else if (d.fmt == kFmtTiff) {
-    const ListId dec = d.tiff.comp == TIFF_LZW ? L_TIFF_LZW : d.tiff.comp == TIFF_DEFLATE ? L_TIFF_INFLATE : L_TIFF_PACKBITS;
+    const ListId dec = d.tiff.comp == TIFF_LZW ? L_TIFF_LZW : d.tiff.comp == TIFF_DEFLATE ? L_TIFF_INFLATE : d.tiff.comp == TIFF_G4 ? L_TIFF_G4 : L_TIFF_PACKBITS;
     for (uint32_t sg = 0; d.tiff.comp != TIFF_NONE && sg < d.tiff.nseg; sg++) b.lists[dec].push_back({I, sg});
-    for (uint32_t it = 0; it < d.height * d.tiff.across; it += kTiffExpandPieces) b.lists[d.tiff.bits == 16 ? L_TIFF_EXPAND16 : L_TIFF_EXPAND].push_back({I, it});
+    for (uint32_t it = 0; it < d.height * d.tiff.across; it += kTiffExpandPieces) b.lists[d.tiff.bits == 16 ? L_TIFF_EXPAND16 : d.tiff.bits == 1 ? L_TIFF_EXPAND1 : L_TIFF_EXPAND].push_back({I, it});
   } else if (d.fmt == kFmtBmp) {
     if (d.bmp.rle) b.lists[L_BMP_RLE].push_back({I, 0});
     for (uint32_t it = 0; it < bmp_row_groups(d.width) * d.height; it += 64) b.lists[L_BMP_EXPAND].push_back({I, it});

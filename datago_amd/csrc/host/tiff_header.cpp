@@ -41,7 +41,7 @@ struct Entry {
 };
 }  // namespace
 
-void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate, bool deep) {
+void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate, bool deep, bool bilevel) {
   h = TiffHeader();
   if (!is_tiff(d, n)) return fail(h, TH_CORRUPT, "not a TIFF");
   const Reader r{d, n, d[0] == 'M'};
@@ -52,8 +52,8 @@ void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate, 
   const size_t cnt = r.u16(ifd);
   if (cnt == 0 || ifd + 2 + 12 * cnt > n) return fail(h, TH_CORRUPT, "TIFF: IFD reaches past the file");
   // the tags the decode depends on
-  enum { T_W, T_H, T_BITS, T_COMP, T_PHOTO, T_FILL, T_SOFF, T_SPP, T_RPS, T_SCNT, T_PLANAR, T_PRED, T_TW, T_TH, T_TOFF, T_TCNT, T_EXTRA, T_FMT, T_N };
-  static const uint32_t ids[T_N] = {256, 257, 258, 259, 262, 266, 273, 277, 278, 279, 284, 317, 322, 323, 324, 325, 338, 339};
+  enum { T_W, T_H, T_BITS, T_COMP, T_PHOTO, T_FILL, T_SOFF, T_SPP, T_RPS, T_SCNT, T_PLANAR, T_PRED, T_TW, T_TH, T_TOFF, T_TCNT, T_EXTRA, T_FMT, T_T6, T_N };
+  static const uint32_t ids[T_N] = {256, 257, 258, 259, 262, 266, 273, 277, 278, 279, 284, 317, 322, 323, 324, 325, 338, 339, 293};
   Entry e[T_N];
   for (size_t i = 0; i < cnt; i++) {
     const size_t p = ifd + 2 + 12 * i;
@@ -85,10 +85,13 @@ void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate, 
   const uint32_t bits = e[T_BITS].present ? e[T_BITS].get(r, 0) : 1u;
   for (uint32_t k = 0; k < spp; k++) {
     const uint32_t b = e[T_BITS].present ? e[T_BITS].get(r, k) : 1u;
-    if (b != 8u && !(deep && b == 16u)) return fail(h, TH_UNSUPPORTED, "TIFF: samples not 8 bits");
+    if (bilevel && (b == 2u || b == 4u)) return fail(h, TH_UNSUPPORTED, "TIFF: 2- or 4-bit samples");
+    if (b != 8u && !(deep && b == 16u) && !(bilevel && b == 1u)) return fail(h, TH_UNSUPPORTED, "TIFF: samples not 8 bits");
     if (b != bits) return fail(h, TH_UNSUPPORTED, "TIFF: mixed BitsPerSample");  // (deep only: 8 and 16 in one pixel)
   }
-  const uint32_t sb = bits / 8u;  // bytes per sample
+  const bool bi = bits == 1u;                // (bilevel only) eight pixels to a byte, MSB first, rows padded to whole bytes
+  const uint32_t sb = bi ? 1u : bits / 8u;   // bytes per sample in the pixel plane
+  if (bi && spp != 1u) return fail(h, TH_UNSUPPORTED, "TIFF: bilevel with an extra sample");
   if (e[T_FMT].present)
     for (uint32_t k = 0; k < e[T_FMT].count; k++)
       if (e[T_FMT].get(r, k) != 1u) return fail(h, TH_UNSUPPORTED, "TIFF: signed or float samples");
@@ -99,7 +102,14 @@ void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate, 
   if (one(T_FILL, 1) != 1) return fail(h, TH_UNSUPPORTED, "TIFF: FillOrder 2");
   if (pred == 3) return fail(h, TH_UNSUPPORTED, "TIFF: floating-point predictor");
   if (pred != 1 && pred != 2) return fail(h, TH_UNSUPPORTED, "TIFF: unknown predictor");
-  if (comp != TIFF_NONE && comp != TIFF_LZW && comp != TIFF_PACKBITS && !(deflate && comp == TIFF_DEFLATE))
+  if (bi && pred == 2) return fail(h, TH_UNSUPPORTED, "TIFF: predictor 2 on 1-bit samples");  // (libtiff refuses it)
+  if (bi && (comp == 2u || comp == 3u)) return fail(h, TH_UNSUPPORTED, "TIFF: Modified Huffman or Group 3 compression");
+  if (bi && comp == TIFF_G4) {
+    const uint32_t t6 = one(T_T6, 0);
+    if (t6 & 2u) return fail(h, TH_UNSUPPORTED, "TIFF: Group 4 uncompressed mode");
+    if (t6) return fail(h, TH_UNSUPPORTED, "TIFF: T6Options other than 0");
+  }
+  if (comp != TIFF_NONE && comp != TIFF_LZW && !(bi && comp == TIFF_G4) && comp != TIFF_PACKBITS && !(deflate && comp == TIFF_DEFLATE))
     return fail(h, TH_UNSUPPORTED, "TIFF: compression other than none, LZW and PackBits");
   // libtiff has no predictor in the raw and PackBits codecs and ignores the tag; the tiff crate applies it.  Its ZIP codec has one.
   if (pred == 2 && comp != TIFF_LZW && comp != TIFF_DEFLATE) return fail(h, TH_UNSUPPORTED, "TIFF: predictor without LZW");
@@ -138,12 +148,13 @@ void parse_tiff_header(const uint8_t *d, size_t n, TiffHeader &h, bool deflate, 
     h.seg_w = h.width;
     h.seg_h = rps < h.height ? rps : h.height;
   }
+  if (comp == TIFF_G4 && h.seg_w > kTiffG4MaxWidth) return fail(h, TH_UNSUPPORTED, "TIFF: Group 4 row wider than 16,384 pixels");
   h.across = (h.width + h.seg_w - 1) / h.seg_w;
   h.down = (h.height + h.seg_h - 1) / h.seg_h;
   const uint64_t nseg = (uint64_t)h.across * h.down;
   if (eo.count != nseg || ec.count != nseg) return fail(h, TH_CORRUPT, "TIFF: segment table does not fit the image");
   h.segs.resize((size_t)nseg);
-  const uint64_t rowb = (uint64_t)h.seg_w * spp * sb;
+  const uint64_t rowb = bi ? ((uint64_t)h.seg_w + 7u) / 8u : (uint64_t)h.seg_w * spp * sb;
   for (uint32_t s = 0; s < nseg; s++) {
     TiffSegment &g = h.segs[s];
     g.off = eo.get(r, s);

@@ -129,6 +129,9 @@ void launch_tiff_lzw(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32
 void launch_tiff_packbits(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_tiff_expand(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 void launch_tiff_expand16(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);  // 16-bit samples (option "tiff16")
+void launch_tiff_expand1(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);   // 1-bit samples (option "tiff_bilevel")
+// CCITT Group 4 (dg_tiff_g4.hip, option "tiff_bilevel"): one 64-thread workgroup (one wave) per (image, segment)
+void launch_tiff_g4(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // TIFF Deflate (dg_tiff_inflate.hip, option "tiff_deflate"): one 64-thread workgroup (one wave) per (image, segment)
 void launch_tiff_inflate(hipStream_t st, ImageDesc *imgs, const WgItem *list, uint32_t nwg);
 // lossless WebP (dg_vp8l.hip, option "webp"): decode and inverse = one 64-thread workgroup (one wave) per

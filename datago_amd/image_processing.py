@@ -90,8 +90,9 @@ class ARAwareTransform:
     def __init__(self, cfg: ImageTransformConfig, device: int = 0, png16: bool = False, resize16: bool = False,
                  penc_dynamic: bool = False, penc16: bool = False, jenc_optimize: bool = False, gif: bool = False,
                  webp: bool = False, webp_lossy: bool = False, webp_alpha: bool = False, bmp: bool = False,
-                 tiff: bool = False, tiff16: bool = False, penc_match: bool = False):
+                 tiff: bool = False, tiff16: bool = False, penc_match: bool = False, tiff_bilevel: bool = False):
         self.cfg = cfg
+        self.tiff_bilevel = tiff_bilevel  # context option "tiff_bilevel": with tiff, a 1-bit TIFF (CCITT Group 4 too) decodes on the GPU as L8
         self.tiff16 = tiff16  # context option "tiff16": with tiff, a TIFF of 16-bit samples decodes on the GPU as uint16
         self.tiff = tiff  # context option "tiff": an 8-bit chunky TIFF decodes on the GPU as L8 / LA8 / RGB8 / RGBA8
         self.bmp = bmp  # context option "bmp": a Windows bitmap decodes on the GPU as RGB8 / RGBA8
@@ -133,7 +134,7 @@ class ARAwareTransform:
                                           jenc_optimize=self.jenc_optimize,
                                           gif=self.gif, webp=self.webp, webp_lossy=self.webp_lossy,
                                           webp_alpha=self.webp_alpha, bmp=self.bmp, tiff=self.tiff,
-                                          tiff16=self.tiff16)
+                                          tiff16=self.tiff16, tiff_bilevel=self.tiff_bilevel)
         return self._ctx[key]
 
 

@@ -414,6 +414,19 @@ int32_t dg_last_batch_timings(dg_ctx *ctx, const char **names, float *ms, int32_
  *                 mixed BitsPerSample, and an image of width * height * 8 bytes at or over 2^31.  Gray +
  *                 alpha at 16 bits rests on the tiff crate's source alone (libtiff under Pillow does not
  *                 open it).  Any other value: DG_ERR_INVALID
+ *   "tiff_bilevel"  1 = with "tiff" (alone it changes nothing), a TIFF of 1-bit samples decodes as well:
+ *                 BitsPerSample 1 or absent, one sample per pixel, PhotometricInterpretation 0 or 1, FillOrder
+ *                 1, either byte order, strips or tiles with sides that are multiples of 16, compression 1,
+ *                 32773, 5, 8 / 32946 (beside "tiff_deflate") and 4 (CCITT Group 4, T6Options absent or 0).
+ *                 The result is L8 of 0 / 255 with channels 1 and bit_depth 8 (sample 1 is 255 under
+ *                 BlackIsZero, 0 under WhiteIsZero), from there an 8-bit gray PNG's pixels (default 0: such a
+ *                 file stays DG_ERR_UNSUPPORTED "TIFF: samples not 8 bits").  DG_ERR_UNSUPPORTED, each with a
+ *                 text that begins "TIFF: ": Modified Huffman and Group 3 (compression 2 and 3), Group 4's
+ *                 uncompressed mode, predictor 2 on 1-bit samples, 2- and 4-bit samples, an extra sample, a
+ *                 Group 4 row wider than 16,384 pixels, and at completion "TIFF: irregular Group 4 stream"
+ *                 (an invalid or extension code, a run past the row's end, a pass mode without its b1, data
+ *                 that ends before the rows do: libtiff pads such rows, the fax crate fails the file).  Any
+ *                 other value: DG_ERR_INVALID
  *   "webp"     1 = decode still lossless WebP files on the GPU: a RIFF/WEBP file whose image data is a
  *                 VP8L chunk, alone (simple file) or behind VP8X with ICCP / EXIF / XMP / unknown chunks
  *                 skipped (default 0: DG_ERR_CORRUPT from every entry point, like any format the library

@@ -17,6 +17,13 @@ With --deep, the 16-bit legs instead (option "tiff16"; samples = the pool's 8-bi
                      the tests' LZW writer is too slow for files of this size)
     gray16_png, rgb16_png   the same pixels as 16-bit PNGs (options "png16", "resize16")
 
+With --bilevel, the 1-bit legs instead (option "tiff_bilevel"): 2,480 x 3,508 pages (A4 at 300 dpi) of a seeded
+text-like pattern (lines of random 5 x 9 glyphs of 4 x 4-pixel cells), written by Pillow in one strip:
+
+    g4           CCITT Group 4: one strip is one wave's serial walk (k_tiff_g4)
+    bilevel_lzw  LZW over the packed rows
+    gray_png     the same pixels as an 8-bit gray PNG
+
 Pillow's leg there is gray only (decode, to float, Lanczos resize): it holds no 16-bit colour.
 
 and sent through dg_submit_device, device-resident input and output, by one
@@ -48,6 +55,8 @@ W, H = 1024, 1536
 KINDS = ("raw", "lzw", "lzw_pred", "deflate", "deflate_pred", "png")
 TIFFS = KINDS[:5]
 KINDS16 = ("gray16_lzw_pred", "rgb16_raw", "gray16_png", "rgb16_png")
+KINDS1 = ("g4", "bilevel_lzw", "gray_png")
+PAGE = (2480, 3508)
 
 
 def make_pool(distinct: int):
@@ -81,6 +90,34 @@ def make_pool16(distinct: int):
             pool[kind].append(buf.getvalue())
         pool["rgb16_raw"].append(tiff16_craft.tiff16("", px, be=True)[1])
         pool["rgb16_png"].append(synth.encode_png16(px, 2, np.random.default_rng(i)))
+    return pool
+
+
+def text_page(seed: int):
+    """A page of 0 / 255: lines of random glyphs, words apart, margins around."""
+    rng = np.random.default_rng(seed)
+    w, h = PAGE[0] // 4, PAGE[1] // 4
+    cells = np.ones((h, w), np.uint8)
+    n = (w - 80) // 6
+    for y in range(40, h - 50, 14):
+        g = (rng.random((9, n, 6)) > 0.4).astype(np.uint8)
+        g[:, :, 5] = 1
+        g[:, rng.random(n) < 0.15] = 1
+        cells[y:y + 9, 40:40 + 6 * n] = g.reshape(9, 6 * n)
+    return np.kron(cells, np.ones((4, 4), np.uint8))[:PAGE[1], :PAGE[0]] * 255
+
+
+def make_pool1(distinct: int):
+    from PIL import Image
+    pool = {k: [] for k in KINDS1}
+    for i in range(distinct):
+        px = text_page(900 + i)
+        for kind, im, kw in (("g4", px, dict(format="TIFF", compression="group4", tiffinfo={278: PAGE[1]})),
+                             ("bilevel_lzw", px, dict(format="TIFF", compression="tiff_lzw", tiffinfo={278: PAGE[1]})),
+                             ("gray_png", None, dict(format="PNG"))):
+            buf = io.BytesIO()
+            (Image.fromarray(px) if im is None else Image.fromarray(px).convert("1")).save(buf, **kw)
+            pool[kind].append(buf.getvalue())
     return pool
 
 
@@ -164,9 +201,13 @@ def main() -> int:
     ap.add_argument("--no-pillow", action="store_true")
     ap.add_argument("--out", default="")
     ap.add_argument("--deep", action="store_true", help="the 16-bit legs (option tiff16) instead")
+    ap.add_argument("--bilevel", action="store_true", help="the 1-bit legs (option tiff_bilevel) instead")
     a = ap.parse_args()
-    kinds, tiffs = (KINDS16, KINDS16[:2]) if a.deep else (KINDS, TIFFS)
-    pool = make_pool16(a.distinct) if a.deep else make_pool(a.distinct)
+    global W, H
+    if a.bilevel:
+        W, H = PAGE
+    kinds, tiffs = (KINDS1, KINDS1[:2]) if a.bilevel else (KINDS16, KINDS16[:2]) if a.deep else (KINDS, TIFFS)
+    pool = make_pool1(a.distinct) if a.bilevel else make_pool16(a.distinct) if a.deep else make_pool(a.distinct)
     res = {"images": a.n, "distinct": a.distinct, "size": [W, H], "coded_bytes": {k: len(v[0]) for k, v in pool.items()}}
     from oracle import buckets as B
     size = B.ARAwareTransform(512, 16, 0.5, 2.0).target_size(W, H)
@@ -178,12 +219,12 @@ def main() -> int:
     kw = dict(crop_and_resize=True, default_image_size=512, downsampling_ratio=16, min_aspect_ratio=0.5,
               max_aspect_ratio=2.0)
     for kind in kinds:
-        ctx = L.Context(0, tiff=True, tiff_deflate=True, tiff16=a.deep, png16=a.deep, resize16=a.deep, **kw)
+        ctx = L.Context(0, tiff=True, tiff_deflate=True, tiff16=a.deep, png16=a.deep, resize16=a.deep, tiff_bilevel=a.bilevel, **kw)
         res[kind] = run(ctx, L, [pool[kind][i % a.distinct] for i in range(a.n)], a.steps, a.warmup)
         ctx.close()
     r = lambda k: res[k]["images_per_s_pipelined"]  # noqa: E731
     for kind in tiffs:
-        res["%s_over_png" % kind] = round(r(kind) / r(kind[:kind.index("_")] + "_png" if a.deep else "png"), 3)
+        res["%s_over_png" % kind] = round(r(kind) / r("gray_png" if a.bilevel else kind[:kind.index("_")] + "_png" if a.deep else "png"), 3)
         if not a.no_pillow and kind in res["pillow"]:
             res["%s_over_pillow" % kind] = round(r(kind) / res["pillow"][kind]["images_per_s"], 2)
     print(json.dumps(res))
